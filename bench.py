@@ -9,8 +9,15 @@ HIP voxelize(+mean) -> 12 sparse convs (HIP rulebooks + MFMA gather-GEMM) + BN/R
 BEV backbone (MIOpen) -> anchor head -> batched target assignment -> losses -> backward (HIP dgrad/wgrad) ->
 grad-clip -> Adam. Inputs are resident in HBM before the timed region. N>1: DDP over RCCL, weak scaling.
 
-Extra objects on the JSON line: `roofline` (dominant hand-written kernel: subm gather-GEMM, HIP events on the launch
-stream inside the timed region, algorithmic bytes per SURVEY §8d) and `cpu_baseline` (oracle CPU port on a bounded
+A plain run sets up, warms up, times exactly --steps steps and prints the line. --dump-outputs DIR then runs the training step
+once more, untimed, on the batch of the last timed step but from the seeded initial state and in torch's deterministic mode, and
+writes what it handed its caller (loss and its parts, the parameter gradients, the parameters and BatchNorm statistics after the
+optimizer step) as float32 DIR/<name>.npy: the same bits from run to run (see dump_outputs), so two builds can be compared output
+for output.
+
+--full adds everything else, as extra objects on the same line: `roofline` and `kernel_table` (HIP event pairs around the
+hand-written kernels inside the timed steps, algorithmic bytes per SURVEY §8d), the optimizer-less steps (`fwd_bwd_only`), the
+MIOpen A/B leg, the opt-in split-bf16 leg, the PV-RCNN and CRB scoring legs and `cpu_baseline` (oracle CPU port on a bounded
 sample; rank 0, N=1 only)."""
 import argparse
 import gc
@@ -47,6 +54,12 @@ def parse():
     ap.add_argument('--gpus', type=int, default=1)
     ap.add_argument('--steps', type=int, default=20)
     ap.add_argument('--warmup', type=int, default=5)
+    ap.add_argument('--full', action='store_true',
+                    help='also run the legs and tables beside `value` (roofline, kernel tables, fwd_bwd_only, MIOpen / bf16x3 A/B, '
+                         'PV-RCNN, CRB scoring, cpu_baseline); the options that size those legs apply only with --full')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='after the timed steps, run the step of the last one again from the seeded initial state in deterministic mode and '
+                         'write its outputs as float32 DIR/<name>.npy (rank 0)')
     ap.add_argument('--batch', type=int, default=16, help='frames per GPU')
     ap.add_argument('--points', type=int, default=20000)
     ap.add_argument('--kind', default='kitti', choices=['kitti', 'waymo'])
@@ -745,6 +758,39 @@ def pvrcnn_bench(args, rank, world, device):
     return out
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(path, model, loss, tb):
+    """--dump-outputs: what the dumped step handed its caller, as float32 `<name>.npy` files - `loss`, `tb.<key>` (the
+    loss parts), `grad.<parameter>` (the gradients after grad-clip), `param.<parameter>` and `buffer.<name>` (the state after
+    the optimizer step and the train-mode BatchNorm updates). SECOND: 230 files, 49 MB.
+
+    Why not the last timed step itself: the loop trains, and in the default mode the weight gradients of two BEV-backbone layers
+    (MIOpen's split-K kernels for the stride-2 and the transposed convolution) add their partials with atomics,
+    so after a few steps the parameters - and with them every later output - drift apart from run to run far beyond rounding.
+    The step dumped starts from the seeded initial parameters and an empty optimizer state instead. Even then AdamW's first step
+    (g / (|g| + eps)) turns the rounding of those two gradients into parameter differences of up to 2e-4 of the tensor's largest
+    entry, so the step runs under torch.use_deterministic_algorithms: the same code path, except that those two weight gradients
+    come from the project's gather-GEMM weight-gradient kernel in a fixed order (crbhip/dense_strided.py, within 2e-4 of the
+    default mode's: tests/test_determinism.py). Every output is then bit-equal from run to run."""
+    arrays = {'loss': loss}
+    arrays.update(('tb.' + k, v) for k, v in tb.items() if torch.is_tensor(v) or isinstance(v, (int, float)))
+    for name, p in model.named_parameters():
+        arrays['param.' + name] = p
+        if p.grad is not None:
+            arrays['grad.' + name] = p.grad
+    arrays.update(('buffer.' + name, b) for name, b in model.named_buffers() if b.is_floating_point())
+    arrays = {k: np.asarray(v.detach().float().cpu().numpy() if torch.is_tensor(v) else v, dtype=np.float32)
+              for k, v in arrays.items()}
+    total = sum(a.nbytes for a in arrays.values())
+    assert total <= DUMP_LIMIT_BYTES, 'outputs of one step are %d bytes, more than the %d allowed' % (total, DUMP_LIMIT_BYTES)
+    os.makedirs(path, exist_ok=True)
+    for k, a in arrays.items():
+        np.save(os.path.join(path, k + '.npy'), a)
+    return len(arrays), total
+
+
 def main():
     args = parse()
     rank = int(os.environ.get('RANK', 0))
@@ -799,13 +845,18 @@ def main():
         net = torch.nn.parallel.DistributedDataParallel(model, device_ids=[dev_idx], gradient_as_bucket_view=True,
                                                         bucket_cap_mb=DDP_BUCKET_MB)
     batches = make_batches(args, rank, device)
+    # --dump-outputs: the seeded starting state, to run the dumped step from (dump_outputs)
+    init_state = {k: v.detach().clone() for k, v in model.state_dict().items()} if args.dump_outputs else None
 
     ahead = {}                                   # step index -> batch dict whose sparse prologue is already enqueued
+    last_tb = {}                                 # the loss parts of the latest step (--dump-outputs)
 
     def step(i, optimizer=True):
         b = ahead.pop(i, None) or dict(batches[i % len(batches)])
         opt.zero_grad(set_to_none=True)
         ret, tb, _ = net(b)
+        last_tb.clear()
+        last_tb.update(tb)
         if not args.no_sparse_prefetch:
             # loader-side work of the NEXT step (voxel generator, marking half of the table plan) goes into the queue before this
             # step's backward pass; its counts reach pinned memory long before the next forward pass asks for them
@@ -862,17 +913,36 @@ def main():
     # two 8 - 12 ms holes per 8 steps in the kernel trace, step-time p90 50 ms against a 44 ms median)
     gc.collect()
     gc.freeze()
-    overhead_ms = event_pair_overhead_ms() if rank == 0 else 0.0
-    prof = [] if rank == 0 else None
+    # --full: HIP event pairs around the hand-written kernels of the timed steps (rank 0) for `roofline` / `kernel_table`
+    overhead_ms = event_pair_overhead_ms() if rank == 0 and args.full else 0.0
+    prof = [] if rank == 0 and args.full else None
     torch.cuda.reset_peak_memory_stats()
     dt, per_step, loss = timed_steps(True, prof)
     peak_main = torch.cuda.max_memory_allocated()
+    dumped = None
+    if args.dump_outputs:
+        # the training step once more, on the last timed step's batch, from the seeded initial state and a fresh optimizer, in the
+        # deterministic mode (dump_outputs); every rank: the DDP all-reduce of the step needs them all. Untimed
+        model.load_state_dict(init_state)
+        opt.state.clear()
+        keep = torch.are_deterministic_algorithms_enabled(), torch.is_deterministic_algorithms_warn_only_enabled()
+        torch.use_deterministic_algorithms(True, warn_only=True)
+        try:
+            loss_dump = step(args.steps - 1)
+            torch.cuda.synchronize()
+        finally:
+            torch.use_deterministic_algorithms(keep[0], warn_only=keep[1])
+        if rank == 0:
+            dumped = dump_outputs(args.dump_outputs, model, loss_dump, last_tb)
+        init_state = None
     # the same step without grad-clip / AdamW ("one optimizer-less loss.backward() step"); not profiled
-    dt_nopt, per_step_nopt, _ = timed_steps(False, None)
+    dt_nopt, per_step_nopt = None, None
+    if args.full:
+        dt_nopt, per_step_nopt, _ = timed_steps(False, None)
     # OPT-IN split-bf16 gather-GEMM (spconv.pytorch.set_arithmetic(model, 'bf16x3')): a few more steps of the same training loop with
     # the contract switched on, only to report its roofline and step time beside the exact-f32 ones; never part of `value`
     prof3, dt3, per_step3 = ([] if rank == 0 else None), None, None
-    if args.bf16x3_steps > 0:
+    if args.full and args.bf16x3_steps > 0:
         import spconv.pytorch as spconv_mirror
         spconv_mirror.set_arithmetic(model, 'bf16x3')
         try:
@@ -887,7 +957,7 @@ def main():
     # A/B: the same training loop for a few more steps with MIOpen's implicit GEMM for the stride-1 3x3 convolutions of the BEV
     # backbone (CRB_WINOGRAD=0) instead of the hand-written Winograd F(2x2,3x3) kernel (crbhip.winograd) that `value` runs
     miopen = None
-    if args.miopen_steps > 0:
+    if args.full and args.miopen_steps > 0:
         from pcdet.models.backbones_2d import base_bev_backbone as bev
         keep_flag, bev.WINOGRAD = bev.WINOGRAD, False
         try:
@@ -921,15 +991,19 @@ def main():
                    'final_loss': round(float(loss.item()), 4)},
         'ms_per_step_device': _pctl(per_step), 'peak_mem_GB': round(peak_main / 2 ** 30, 1),
         'ms_per_step_device_per_rank': rank_step_ms[0], 'ms_per_step_per_rank': rank_wall_ms[0],
-        'warmup_seconds_per_rank': [round(v, 3) for v in warm_s], 'miopen_user_db': miopen_db,
-        'fwd_bwd_only': {'value': round(frames / dt_nopt, 3), 'unit': 'frames/s',
-                         'ms_per_step': round(1e3 * dt_nopt / args.steps, 3), 'ms_per_step_device': _pctl(per_step_nopt),
-                         'note': 'same %d steps without grad-clip / optimizer' % args.steps},
+        'warmup_seconds_per_rank': [round(v, 3) for v in warm_s], 'miopen_user_db': miopen_db, 'full': args.full,
     }
+    if dumped is not None:
+        out['dumped_outputs'] = {'files': dumped[0], 'bytes': dumped[1], 'loss': float(loss_dump.item()),
+                                 'step': 'batch of timed step %d, from the seeded initial state, deterministic mode' % args.steps}
+    if args.full:
+        out['fwd_bwd_only'] = {'value': round(frames / dt_nopt, 3), 'unit': 'frames/s',
+                               'ms_per_step': round(1e3 * dt_nopt / args.steps, 3), 'ms_per_step_device': _pctl(per_step_nopt),
+                               'note': 'same %d steps without grad-clip / optimizer' % args.steps}
     # the kernel tables come out of the event records NOW: the records hold the rulebook tables of every profiled step (device
     # memory: until r04 they stayed alive through the later legs and sat in their peak-memory numbers, 12 GB of the "40.9 GB")
-    roof_pack = None
-    if rank == 0:
+    roof_pack = (None, None, {})
+    if rank == 0 and args.full:
         roof_g, table_g = roofline_from_profile(prof, overhead_ms)
         roof_pack = dominant_roofline(prof, overhead_ms, roof_g, table_g)
         roof3_pack = roofline_from_profile(prof3, overhead_ms, 'bf16x3') if dt3 is not None else None
@@ -937,8 +1011,9 @@ def main():
     del opt, net, model, batches
     gc.collect()
     torch.cuda.empty_cache()
-    pv = pvrcnn_bench(args, rank, world, device) if (args.pvrcnn_steps > 0 and args.kind == 'kitti') else None
-    score = crb_scoring_bench(args, rank, world, device) if (args.scoring_pool > 0 and args.kind == 'kitti') else None
+    legs = args.full and args.kind == 'kitti'
+    pv = pvrcnn_bench(args, rank, world, device) if (legs and args.pvrcnn_steps > 0) else None
+    score = crb_scoring_bench(args, rank, world, device) if (legs and args.scoring_pool > 0) else None
     if rank == 0:
         roof, gather_roof, table = roof_pack
         # the numbers a reader looks for first, once at the head of the line and once at its very end (a log tail keeps the end)
@@ -967,17 +1042,18 @@ def main():
         first['headline'] = headline
         first.update({k: v for k, v in out.items() if k not in first})
         out = first
-        out['roofline'] = roof
-        if gather_roof is not None:
-            out['roofline_gather_gemm'] = gather_roof
-        if world == 1 and not args.no_cpu_baseline:
-            out['cpu_baseline'] = cpu_baseline(args)
-        else:
-            out['cpu_baseline'] = None
-        out['crb_scoring'] = score
-        out['pvrcnn'] = pv
-        out['miopen_convs'] = miopen
-        out['kernel_table'] = table
+        if args.full:
+            out['roofline'] = roof
+            if gather_roof is not None:
+                out['roofline_gather_gemm'] = gather_roof
+            if world == 1 and not args.no_cpu_baseline:
+                out['cpu_baseline'] = cpu_baseline(args)
+            else:
+                out['cpu_baseline'] = None
+            out['crb_scoring'] = score
+            out['pvrcnn'] = pv
+            out['miopen_convs'] = miopen
+            out['kernel_table'] = table
         if dt3 is not None:
             roof3, table3 = roof3_pack
             out['roofline_bf16x3'] = roof3

@@ -190,7 +190,7 @@ def test_bench_two_rank_dry_run_prints_the_contract_line(tmp_path):
     env = dict(os.environ, CRB_DIST_BACKEND='gloo', MASTER_ADDR='127.0.0.1', HSA_ENABLE_IPC_MODE_LEGACY='0')
     pool = 64
     cmd = [sys.executable, '-m', 'torch.distributed.run', '--nnodes=1', '--nproc-per-node', '2', '--master-addr', '127.0.0.1',
-           '--master-port', '29541', os.path.join(root, 'bench.py'), '--gpus', '2', '--steps', '2', '--warmup', '1',
+           '--master-port', '29541', os.path.join(root, 'bench.py'), '--gpus', '2', '--steps', '2', '--warmup', '1', '--full',
            '--scoring-pool', str(pool), '--scoring-repeats', '1', '--pvrcnn-steps', '0', '--bf16x3-steps', '0',
            '--no-cpu-baseline', '--n1-value', '100.0']
     r = subprocess.run(cmd, env=env, cwd=root, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=900)
@@ -295,7 +295,7 @@ def test_bench_one_rank_over_rccl_prints_the_contract_line():
     env = dict(os.environ, CRB_FORCE_DIST='1', MASTER_ADDR='127.0.0.1', HSA_ENABLE_IPC_MODE_LEGACY='0')
     env.pop('CRB_DIST_BACKEND', None)
     cmd = [sys.executable, '-m', 'torch.distributed.run', '--nnodes=1', '--nproc-per-node', '1', '--master-addr', '127.0.0.1',
-           '--master-port', '29547', os.path.join(ROOT, 'bench.py'), '--gpus', '1', '--steps', '2', '--warmup', '1',
+           '--master-port', '29547', os.path.join(ROOT, 'bench.py'), '--gpus', '1', '--steps', '2', '--warmup', '1', '--full',
            '--scoring-pool', '32', '--scoring-repeats', '1', '--pvrcnn-steps', '0', '--bf16x3-steps', '0', '--no-cpu-baseline']
     r = subprocess.run(cmd, env=env, cwd=ROOT, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-3000:]
