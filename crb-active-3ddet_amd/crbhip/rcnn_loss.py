@@ -71,6 +71,62 @@ def rcnn_loss(rcnn_cls, rcnn_reg, cls_labels, reg_valid_mask, rois, gt_of_rois, 
                            f(rois).view(n, 7), f(gt_of_rois).view(n, c), f(gt_of_rois_src).view(n, c), cfg)
 
 
+class _RcnnLossPerFrame(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, rcnn_cls, rcnn_reg, labels, reg_valid, rois, gt_local, gt_src, B, cfg):
+        n = int(rcnn_reg.shape[0])
+        dev = rcnn_reg.device
+        parts = torch.empty((B, 4), dtype=torch.float32, device=dev)
+        d_cls = torch.empty((n,), dtype=torch.float32, device=dev)
+        d_reg = torch.empty((n, 7), dtype=torch.float32, device=dev)
+        tgt = torch.empty((n, 7), dtype=torch.float32, device=dev)
+        check(lib.crb_rcnn_loss_per_frame(ptr(rcnn_cls), ptr(rcnn_reg), ptr(labels), int(labels.dtype == torch.int64), ptr(reg_valid),
+                                          ptr(rois), ptr(gt_local), ptr(gt_src), int(gt_local.shape[1]), n, B, ctypes.byref(cfg),
+                                          ptr(parts), ptr(d_cls), ptr(d_reg), ptr(tgt), cur_stream(dev)), 'crb_rcnn_loss_per_frame')
+        ctx.save_for_backward(d_cls, d_reg)
+        ctx.shapes, ctx.B = (rcnn_cls.shape, rcnn_reg.shape), B
+        total = parts[:, 3].clone()
+        ctx.mark_non_differentiable(parts, tgt)
+        ctx.set_materialize_grads(False)
+        return total, parts, tgt
+
+    @staticmethod
+    def backward(ctx, g, _gp, _gt):
+        if g is None:
+            return (None,) * 9
+        d_cls, d_reg = ctx.saved_tensors
+        return (scale_rows_per_frame(d_cls, g, ctx.B).view(ctx.shapes[0]), scale_rows_per_frame(d_reg, g, ctx.B).view(ctx.shapes[1]),
+                None, None, None, None, None, None, None)
+
+
+def scale_rows_per_frame(d, g, B):
+    """d (rows, ...) per-row gradients for a unit upstream value per frame, g (B,) -> d * g[frame of the row]"""
+    g = g.contiguous().float()
+    out = torch.empty_like(d)
+    rows = int(d.shape[0])
+    check(lib.crb_scale_rows_per_frame(ptr(d), rows, int(d.numel() // max(rows, 1)), int(B), ptr(g), ptr(out), cur_stream(d.device)),
+          'crb_scale_rows_per_frame')
+    return out
+
+
+def rcnn_loss_per_frame(rcnn_cls, rcnn_reg, cls_labels, reg_valid_mask, rois, gt_of_rois, gt_of_rois_src, cfg):
+    """the reduce=False form of rcnn_loss: same inputs with B = rois.shape[0] frames -> (per-frame rcnn_loss (B,) with the graph,
+    parts (B, 4) = {cls, reg, corner, total} per frame detached, reg_targets (n,7))"""
+    require_cuda(rcnn_cls, rcnn_reg, cls_labels, reg_valid_mask, rois, gt_of_rois, gt_of_rois_src)
+    n, B = int(rcnn_reg.shape[0]), int(rois.shape[0])
+    if rcnn_reg.shape[-1] != 7 or rcnn_cls.numel() != n or cls_labels.numel() != n or reg_valid_mask.numel() != n or \
+            rois.numel() != n * 7 or gt_of_rois.numel() != gt_of_rois_src.numel() or gt_of_rois.shape[-1] < 7 or n % B != 0:
+        raise CrbHipError('crb_rcnn_loss_per_frame: tensor sizes do not match n = %d RoIs of code size 7 in %d frames' % (n, B))
+    if cls_labels.dtype not in (torch.float32, torch.int64):
+        cls_labels = cls_labels.float()
+    if reg_valid_mask.dtype != torch.int64:
+        reg_valid_mask = reg_valid_mask.long()
+    c = gt_of_rois.shape[-1]
+    f = lambda t: t.contiguous().float()
+    return _RcnnLossPerFrame.apply(f(rcnn_cls).view(n), f(rcnn_reg), cls_labels.contiguous().view(n), reg_valid_mask.contiguous().view(n),
+                                   f(rois).view(n, 7), f(gt_of_rois).view(n, c), f(gt_of_rois_src).view(n, c), B, cfg)
+
+
 @torch.no_grad()
 def roi_canonical_targets(rois, gt_of_rois):
     """rois (B,P,7+), gt_of_rois (B,P,7+C) in LiDAR coordinates -> the same boxes in the RoI frame, heading folded into

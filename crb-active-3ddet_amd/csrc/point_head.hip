@@ -76,6 +76,39 @@ __global__ __launch_bounds__(TPB) void point_focal_loss_kernel(const float* __re
   }
 }
 
+// reduce=False form (point_head_template.py:131-155 with reduce=False): the focal terms summed per frame of n / B points, the
+// normaliser the whole batch's positives; gradients for a unit upstream value of every frame's sum. out (B + 1) = per-frame losses
+// (x loss_weight), positives.
+__global__ __launch_bounds__(TPB) void point_focal_loss_frames_kernel(const float* __restrict__ preds, const int64_t* __restrict__ labels,
+                                                                      int64_t n, int C, int B, float alpha, float gamma, float weight,
+                                                                      float* __restrict__ out, float* __restrict__ d_preds) {
+  __shared__ float sh[TPB / 64];
+  float np = 0.f;
+  for (int64_t i = threadIdx.x; i < n; i += TPB) np += labels[i] > 0 ? 1.f : 0.f;
+  const float pos = block_sum(np, sh);
+  const float w = 1.0f / fmaxf(pos, 1.0f);
+  const int64_t M = n / B;
+  for (int f = 0; f < B; ++f) {
+    float s = 0.f;
+    for (int64_t i = f * M + threadIdx.x; i < (f + 1) * M; i += TPB) {
+      const int64_t lab = labels[i];
+      for (int c = 0; c < C; ++c) {
+        float l = 0.f, d = 0.f;
+        if (lab >= 0) {
+          focal_term(preds[i * C + c], lab == c + 1, alpha, gamma, l, d);
+          l *= w;
+          d *= w * weight;
+        }
+        s += l;
+        d_preds[i * C + c] = d;
+      }
+    }
+    const float total = block_sum(s, sh);
+    if (threadIdx.x == 0) out[f] = total * weight;
+  }
+  if (threadIdx.x == 0) out[B] = pos;
+}
+
 __global__ __launch_bounds__(256) void point_labels_kernel(const int32_t* __restrict__ inner, const int32_t* __restrict__ outer,
                                                            const float* __restrict__ gt, int64_t n, int M, int G, int gt_c, int num_class,
                                                            int64_t* __restrict__ labels) {
@@ -96,6 +129,15 @@ extern "C" int crb_point_focal_loss(const float* preds, const int64_t* labels, i
   if (n > 0 && (!preds || !labels || !d_preds)) return CRB_ERR_ARG;
   hipLaunchKernelGGL(point_focal_loss_kernel, dim3(1), dim3(TPB), 0, (hipStream_t)stream, preds, labels, n, num_class, alpha, gamma,
                      loss_weight, loss, d_preds);
+  CRB_CHECK_LAUNCH();
+  return CRB_OK;
+}
+
+extern "C" int crb_point_focal_loss_per_frame(const float* preds, const int64_t* labels, int64_t n, int num_class, int B, float alpha,
+                                              float gamma, float loss_weight, float* loss, float* d_preds, void* stream) {
+  if (n <= 0 || n >= (1LL << 24) || num_class <= 0 || B <= 0 || n % B != 0 || !loss || !preds || !labels || !d_preds) return CRB_ERR_ARG;
+  hipLaunchKernelGGL(point_focal_loss_frames_kernel, dim3(1), dim3(TPB), 0, (hipStream_t)stream, preds, labels, n, num_class, B, alpha,
+                     gamma, loss_weight, loss, d_preds);
   CRB_CHECK_LAUNCH();
   return CRB_OK;
 }

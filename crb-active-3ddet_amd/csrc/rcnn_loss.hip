@@ -65,6 +65,115 @@ __device__ __forceinline__ void corner_of(int k, float& tx, float& ty, float& tz
   tz = k < 4 ? -0.5f : 0.5f;
 }
 
+// one RoI: its BCE term, smooth-L1 row and corner term (mean over the 8 corners) added to s_cls / s_reg / s_cor, and their
+// gradients scaled by w_cls / den_v, w_reg / den_f and w_corner / den_c written to d_cls[i], d_reg[i]
+__device__ __forceinline__ void rcnn_row(const RcnnArgs& a, int i, float den_v, float den_f, float den_c, float& s_cls, float& s_reg,
+                                         float& s_cor) {
+  // ---- classification: binary cross entropy on sigmoid(x) (ATen's kernels: log clamped at -100, backward through
+  //      (p - y) / max((1 - p) p, 1e-12) and the sigmoid's (1 - p) p)
+  const float lab = a.labels_i64 ? (float)reinterpret_cast<const int64_t*>(a.labels)[i] : reinterpret_cast<const float*>(a.labels)[i];
+  float gc = 0.f;
+  if (lab >= 0.f) {
+    const float x = a.cls[i];
+    const float p = 1.0f / (1.0f + expf(-x));
+    const float lp = fmaxf(logf(p), -100.f), l1p = fmaxf(log1pf(-p), -100.f);
+    s_cls += (lab - 1.f) * l1p - lab * lp;
+    gc = (p - lab) / fmaxf((1.f - p) * p, 1e-12f) * ((1.f - p) * p) * (a.w_cls / den_v);
+  }
+  a.d_cls[i] = gc;
+  // ---- regression
+  const float* e = a.reg + (int64_t)i * 7;
+  const float* roi = a.rois + (int64_t)i * 7;
+  const float* gl = a.gt_local + (int64_t)i * a.gt_stride;
+  const bool fg = a.reg_valid[i] > 0;
+  float ge[7] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+  float tgt[7];
+  {
+    // ResidualCoder.encode_torch against the anchor (0, 0, 0, roi dims, 0)
+    const float dxa = fmaxf(roi[3], 1e-5f), dya = fmaxf(roi[4], 1e-5f), dza = fmaxf(roi[5], 1e-5f);
+    const float dxg = fmaxf(gl[3], 1e-5f), dyg = fmaxf(gl[4], 1e-5f), dzg = fmaxf(gl[5], 1e-5f);
+    const float diag = sqrtf(dxa * dxa + dya * dya);
+    tgt[0] = gl[0] / diag; tgt[1] = gl[1] / diag; tgt[2] = gl[2] / dza;
+    tgt[3] = logf(dxg / dxa); tgt[4] = logf(dyg / dya); tgt[5] = logf(dzg / dza);
+    tgt[6] = gl[6];
+  }
+  if (a.reg_targets) {
+#pragma unroll
+    for (int j = 0; j < 7; ++j) a.reg_targets[(int64_t)i * 7 + j] = tgt[j];
+  }
+  if (fg) {
+    float row = 0.f;
+#pragma unroll
+    for (int j = 0; j < 7; ++j) {
+      float diff = isnan(tgt[j]) ? 0.f : e[j] - tgt[j];
+      diff *= a.cw[j];
+      const float m = fabsf(diff);
+      float l, g;
+      if (a.beta < 1e-5f) {
+        l = m;
+        g = diff > 0.f ? 1.f : diff < 0.f ? -1.f : 0.f;
+      } else if (m < a.beta) {
+        l = 0.5f * m * m / a.beta;
+        g = diff / a.beta;
+      } else {
+        l = m - 0.5f * a.beta;
+        g = diff > 0.f ? 1.f : -1.f;
+      }
+      row += l;
+      ge[j] = g * a.cw[j] * (a.w_reg / den_f);
+    }
+    s_reg += row;
+    if (a.corner) {
+      // decode against (0, 0, 0, roi dims, roi ry), turn the centre by roi ry, move to the RoI centre
+      const float* gs = a.gt_src + (int64_t)i * a.gt_stride;
+      const float dxa = roi[3], dya = roi[4], dza = roi[5], ra = roi[6];
+      const float diag = sqrtf(dxa * dxa + dya * dya);
+      const float xl = e[0] * diag, yl = e[1] * diag, zl = e[2] * dza;
+      const float dx = expf(e[3]) * dxa, dy = expf(e[4]) * dya, dz = expf(e[5]) * dza;
+      const float rg = e[6] + ra;
+      const float ca = cosf(ra), sa = sinf(ra);
+      const float cx = xl * ca - yl * sa + roi[0], cy = xl * sa + yl * ca + roi[1], cz = zl + roi[2];
+      const float cg = cosf(rg), sg = sinf(rg);
+      const float c1 = cosf(gs[6]), s1 = sinf(gs[6]);
+      const float rf = gs[6] + PI_F;
+      const float c2 = cosf(rf), s2 = sinf(rf);
+      float tot = 0.f, dcx = 0.f, dcy = 0.f, dcz = 0.f, ddx = 0.f, ddy = 0.f, ddz = 0.f, drg = 0.f;
+#pragma unroll
+      for (int k = 0; k < 8; ++k) {
+        float tx, ty, tz;
+        corner_of(k, tx, ty, tz);
+        const float lx = dx * tx, ly = dy * ty, lz = dz * tz;
+        const float px = lx * cg - ly * sg + cx, py = lx * sg + ly * cg + cy, pz = lz + cz;
+        const float gx = gs[3] * tx, gy = gs[4] * ty, gz = gs[5] * tz + gs[2];
+        const float q1x = gx * c1 - gy * s1 + gs[0], q1y = gx * s1 + gy * c1 + gs[1];
+        const float q2x = gx * c2 - gy * s2 + gs[0], q2y = gx * s2 + gy * c2 + gs[1];
+        const float u1x = px - q1x, u1y = py - q1y, u2x = px - q2x, u2y = py - q2y, uz = pz - gz;
+        const float d1 = sqrtf(u1x * u1x + u1y * u1y + uz * uz), d2 = sqrtf(u2x * u2x + u2y * u2y + uz * uz);
+        const float d = fminf(d1, d2);
+        tot += d < 1.f ? 0.5f * d * d : d - 0.5f;
+        const float sl = (d < 1.f ? d : 1.f) * 0.125f;          // d smooth-l1 / d dist, mean over the 8 corners
+        // torch.min gives half of the gradient to each side of a tie; the norm's gradient at 0 is 0
+        const float w1 = d1 < d2 ? 1.f : d1 == d2 ? 0.5f : 0.f, w2 = 1.f - w1;
+        const float i1 = d1 > 0.f ? sl * w1 / d1 : 0.f, i2 = d2 > 0.f ? sl * w2 / d2 : 0.f;
+        const float gpx = i1 * u1x + i2 * u2x, gpy = i1 * u1y + i2 * u2y, gpz = (i1 + i2) * uz;
+        dcx += gpx; dcy += gpy; dcz += gpz;
+        ddx += gpx * (tx * cg) + gpy * (tx * sg);
+        ddy += gpy * (ty * cg) - gpx * (ty * sg);
+        ddz += gpz * tz;
+        drg += gpx * (-lx * sg - ly * cg) + gpy * (lx * cg - ly * sg);
+      }
+      s_cor += tot * 0.125f;
+      const float sc = a.w_corner / den_c;
+      const float dxl = dcx * ca + dcy * sa, dyl = dcy * ca - dcx * sa;
+      ge[0] += dxl * diag * sc; ge[1] += dyl * diag * sc; ge[2] += dcz * dza * sc;
+      ge[3] += ddx * dx * sc; ge[4] += ddy * dy * sc; ge[5] += ddz * dz * sc;
+      ge[6] += drg * sc;
+    }
+  }
+#pragma unroll
+  for (int j = 0; j < 7; ++j) a.d_reg[(int64_t)i * 7 + j] = ge[j];
+}
+
 __global__ __launch_bounds__(TPB) void rcnn_loss_kernel(RcnnArgs a) {
   __shared__ float sh[TPB / 64];
   // ---- denominators
@@ -77,111 +186,7 @@ __global__ __launch_bounds__(TPB) void rcnn_loss_kernel(RcnnArgs a) {
   const float n_valid = block_sum(nv, sh), n_fg = block_sum(nf, sh);       // (integers below 2^24: exact in any order)
   const float den_v = fmaxf(n_valid, 1.f), den_f = fmaxf(n_fg, 1.f);
   float s_cls = 0.f, s_reg = 0.f, s_cor = 0.f;
-  for (int i = threadIdx.x; i < a.n; i += TPB) {
-    // ---- classification: binary cross entropy on sigmoid(x) (ATen's kernels: log clamped at -100, backward through
-    //      (p - y) / max((1 - p) p, 1e-12) and the sigmoid's (1 - p) p)
-    const float lab = a.labels_i64 ? (float)reinterpret_cast<const int64_t*>(a.labels)[i] : reinterpret_cast<const float*>(a.labels)[i];
-    float gc = 0.f;
-    if (lab >= 0.f) {
-      const float x = a.cls[i];
-      const float p = 1.0f / (1.0f + expf(-x));
-      const float lp = fmaxf(logf(p), -100.f), l1p = fmaxf(log1pf(-p), -100.f);
-      s_cls += (lab - 1.f) * l1p - lab * lp;
-      gc = (p - lab) / fmaxf((1.f - p) * p, 1e-12f) * ((1.f - p) * p) * (a.w_cls / den_v);
-    }
-    a.d_cls[i] = gc;
-    // ---- regression
-    const float* e = a.reg + (int64_t)i * 7;
-    const float* roi = a.rois + (int64_t)i * 7;
-    const float* gl = a.gt_local + (int64_t)i * a.gt_stride;
-    const bool fg = a.reg_valid[i] > 0;
-    float ge[7] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-    float tgt[7];
-    {
-      // ResidualCoder.encode_torch against the anchor (0, 0, 0, roi dims, 0)
-      const float dxa = fmaxf(roi[3], 1e-5f), dya = fmaxf(roi[4], 1e-5f), dza = fmaxf(roi[5], 1e-5f);
-      const float dxg = fmaxf(gl[3], 1e-5f), dyg = fmaxf(gl[4], 1e-5f), dzg = fmaxf(gl[5], 1e-5f);
-      const float diag = sqrtf(dxa * dxa + dya * dya);
-      tgt[0] = gl[0] / diag; tgt[1] = gl[1] / diag; tgt[2] = gl[2] / dza;
-      tgt[3] = logf(dxg / dxa); tgt[4] = logf(dyg / dya); tgt[5] = logf(dzg / dza);
-      tgt[6] = gl[6];
-    }
-    if (a.reg_targets) {
-#pragma unroll
-      for (int j = 0; j < 7; ++j) a.reg_targets[(int64_t)i * 7 + j] = tgt[j];
-    }
-    if (fg) {
-      float row = 0.f;
-#pragma unroll
-      for (int j = 0; j < 7; ++j) {
-        float diff = isnan(tgt[j]) ? 0.f : e[j] - tgt[j];
-        diff *= a.cw[j];
-        const float m = fabsf(diff);
-        float l, g;
-        if (a.beta < 1e-5f) {
-          l = m;
-          g = diff > 0.f ? 1.f : diff < 0.f ? -1.f : 0.f;
-        } else if (m < a.beta) {
-          l = 0.5f * m * m / a.beta;
-          g = diff / a.beta;
-        } else {
-          l = m - 0.5f * a.beta;
-          g = diff > 0.f ? 1.f : -1.f;
-        }
-        row += l;
-        ge[j] = g * a.cw[j] * (a.w_reg / den_f);
-      }
-      s_reg += row;
-      if (a.corner) {
-        // decode against (0, 0, 0, roi dims, roi ry), turn the centre by roi ry, move to the RoI centre
-        const float* gs = a.gt_src + (int64_t)i * a.gt_stride;
-        const float dxa = roi[3], dya = roi[4], dza = roi[5], ra = roi[6];
-        const float diag = sqrtf(dxa * dxa + dya * dya);
-        const float xl = e[0] * diag, yl = e[1] * diag, zl = e[2] * dza;
-        const float dx = expf(e[3]) * dxa, dy = expf(e[4]) * dya, dz = expf(e[5]) * dza;
-        const float rg = e[6] + ra;
-        const float ca = cosf(ra), sa = sinf(ra);
-        const float cx = xl * ca - yl * sa + roi[0], cy = xl * sa + yl * ca + roi[1], cz = zl + roi[2];
-        const float cg = cosf(rg), sg = sinf(rg);
-        const float c1 = cosf(gs[6]), s1 = sinf(gs[6]);
-        const float rf = gs[6] + PI_F;
-        const float c2 = cosf(rf), s2 = sinf(rf);
-        float tot = 0.f, dcx = 0.f, dcy = 0.f, dcz = 0.f, ddx = 0.f, ddy = 0.f, ddz = 0.f, drg = 0.f;
-#pragma unroll
-        for (int k = 0; k < 8; ++k) {
-          float tx, ty, tz;
-          corner_of(k, tx, ty, tz);
-          const float lx = dx * tx, ly = dy * ty, lz = dz * tz;
-          const float px = lx * cg - ly * sg + cx, py = lx * sg + ly * cg + cy, pz = lz + cz;
-          const float gx = gs[3] * tx, gy = gs[4] * ty, gz = gs[5] * tz + gs[2];
-          const float q1x = gx * c1 - gy * s1 + gs[0], q1y = gx * s1 + gy * c1 + gs[1];
-          const float q2x = gx * c2 - gy * s2 + gs[0], q2y = gx * s2 + gy * c2 + gs[1];
-          const float u1x = px - q1x, u1y = py - q1y, u2x = px - q2x, u2y = py - q2y, uz = pz - gz;
-          const float d1 = sqrtf(u1x * u1x + u1y * u1y + uz * uz), d2 = sqrtf(u2x * u2x + u2y * u2y + uz * uz);
-          const float d = fminf(d1, d2);
-          tot += d < 1.f ? 0.5f * d * d : d - 0.5f;
-          const float sl = (d < 1.f ? d : 1.f) * 0.125f;          // d smooth-l1 / d dist, mean over the 8 corners
-          // torch.min gives half of the gradient to each side of a tie; the norm's gradient at 0 is 0
-          const float w1 = d1 < d2 ? 1.f : d1 == d2 ? 0.5f : 0.f, w2 = 1.f - w1;
-          const float i1 = d1 > 0.f ? sl * w1 / d1 : 0.f, i2 = d2 > 0.f ? sl * w2 / d2 : 0.f;
-          const float gpx = i1 * u1x + i2 * u2x, gpy = i1 * u1y + i2 * u2y, gpz = (i1 + i2) * uz;
-          dcx += gpx; dcy += gpy; dcz += gpz;
-          ddx += gpx * (tx * cg) + gpy * (tx * sg);
-          ddy += gpy * (ty * cg) - gpx * (ty * sg);
-          ddz += gpz * tz;
-          drg += gpx * (-lx * sg - ly * cg) + gpy * (lx * cg - ly * sg);
-        }
-        s_cor += tot * 0.125f;
-        const float sc = a.w_corner / den_f;
-        const float dxl = dcx * ca + dcy * sa, dyl = dcy * ca - dcx * sa;
-        ge[0] += dxl * diag * sc; ge[1] += dyl * diag * sc; ge[2] += dcz * dza * sc;
-        ge[3] += ddx * dx * sc; ge[4] += ddy * dy * sc; ge[5] += ddz * dz * sc;
-        ge[6] += drg * sc;
-      }
-    }
-#pragma unroll
-    for (int j = 0; j < 7; ++j) a.d_reg[(int64_t)i * 7 + j] = ge[j];
-  }
+  for (int i = threadIdx.x; i < a.n; i += TPB) rcnn_row(a, i, den_v, den_f, den_f, s_cls, s_reg, s_cor);
   const float t_cls = block_sum(s_cls, sh), t_reg = block_sum(s_reg, sh), t_cor = block_sum(s_cor, sh);
   if (threadIdx.x == 0) {
     const float l_cls = t_cls / den_v * a.w_cls, l_reg = t_reg / den_f * a.w_reg, l_cor = a.corner ? t_cor / den_f * a.w_corner : 0.f;
@@ -193,6 +198,44 @@ __global__ __launch_bounds__(TPB) void rcnn_loss_kernel(RcnnArgs a) {
     a.out[5] = n_valid;
     a.out[6] = a.out[3];
   }
+}
+
+// reduce=False form (roi_head_template.py:142-285 with reduce=False): the same terms summed per frame of rows_per_frame RoIs; cls
+// and reg divided by the WHOLE batch's valid / foreground counts, corner by the FRAME's foreground count. Gradients are written for
+// a unit upstream value of every frame's total (a row's gradient only involves its own frame's total: the denominators are batch
+// constants). out (B, 4) = {cls, reg, corner, total} per frame; frames in order, each a fixed-order block sum.
+__global__ __launch_bounds__(TPB) void rcnn_loss_frames_kernel(RcnnArgs a, int B, float* __restrict__ out) {
+  __shared__ float sh[TPB / 64];
+  const int P = a.n / B;
+  float nv = 0.f, nf = 0.f;
+  for (int i = threadIdx.x; i < a.n; i += TPB) {
+    const float lab = a.labels_i64 ? (float)reinterpret_cast<const int64_t*>(a.labels)[i] : reinterpret_cast<const float*>(a.labels)[i];
+    nv += lab >= 0.f ? 1.f : 0.f;
+    nf += a.reg_valid[i] > 0 ? 1.f : 0.f;
+  }
+  const float den_v = fmaxf(block_sum(nv, sh), 1.f), den_f = fmaxf(block_sum(nf, sh), 1.f);
+  for (int f = 0; f < B; ++f) {
+    const int r0 = f * P, r1 = r0 + P;
+    float ff = 0.f;
+    for (int i = r0 + threadIdx.x; i < r1; i += TPB) ff += a.reg_valid[i] > 0 ? 1.f : 0.f;
+    const float den_c = fmaxf(block_sum(ff, sh), 1.f);
+    float s_cls = 0.f, s_reg = 0.f, s_cor = 0.f;
+    for (int i = r0 + threadIdx.x; i < r1; i += TPB) rcnn_row(a, i, den_v, den_f, den_c, s_cls, s_reg, s_cor);
+    const float t_cls = block_sum(s_cls, sh), t_reg = block_sum(s_reg, sh), t_cor = block_sum(s_cor, sh);
+    if (threadIdx.x == 0) {
+      const float l_cls = t_cls / den_v * a.w_cls, l_reg = t_reg / den_f * a.w_reg, l_cor = a.corner ? t_cor / den_c * a.w_corner : 0.f;
+      out[f * 4 + 0] = l_cls;
+      out[f * 4 + 1] = l_reg;
+      out[f * 4 + 2] = l_cor;
+      out[f * 4 + 3] = l_cls + (l_reg + l_cor);
+    }
+  }
+}
+
+__global__ __launch_bounds__(256) void scale_rows_kernel(const float* __restrict__ src, int64_t total, int64_t per_frame, const float* __restrict__ g,
+                                                         float* __restrict__ dst) {
+  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (i < total) dst[i] = src[i] * g[i / per_frame];
 }
 
 // gt (n, C >= 7) in LiDAR coordinates -> the RoI's frame: centre relative to the RoI and turned by -ry(roi), heading relative to
@@ -397,6 +440,37 @@ extern "C" int crb_rcnn_loss(const float* rcnn_cls, const float* rcnn_reg, const
   a.w_cls = cfg->cls_weight; a.w_reg = cfg->reg_weight; a.w_corner = cfg->corner_weight;
   a.out = loss; a.d_cls = d_cls; a.d_reg = d_reg; a.reg_targets = reg_targets;
   hipLaunchKernelGGL(rcnn_loss_kernel, dim3(1), dim3(TPB), 0, (hipStream_t)stream, a);
+  CRB_CHECK_LAUNCH();
+  return CRB_OK;
+}
+
+extern "C" int crb_rcnn_loss_per_frame(const float* rcnn_cls, const float* rcnn_reg, const void* cls_labels, int labels_are_int64,
+                                       const int64_t* reg_valid_mask, const float* rois, const float* gt_of_rois, const float* gt_of_rois_src,
+                                       int gt_row_stride, int64_t n, int B, const CrbRcnnLossCfg* cfg, float* loss_frames, float* d_cls,
+                                       float* d_reg, float* reg_targets, void* stream) {
+  if (n <= 0 || n >= (1LL << 24) || B <= 0 || n % B != 0 || !cfg || !loss_frames || gt_row_stride < 7) return CRB_ERR_ARG;
+  if (!rcnn_cls || !rcnn_reg || !cls_labels || !reg_valid_mask || !rois || !gt_of_rois || !d_cls || !d_reg) return CRB_ERR_ARG;
+  if (cfg->corner && !gt_of_rois_src) return CRB_ERR_ARG;
+  RcnnArgs a;
+  a.cls = rcnn_cls; a.reg = rcnn_reg; a.labels = cls_labels; a.reg_valid = reg_valid_mask; a.rois = rois;
+  a.gt_local = gt_of_rois; a.gt_src = gt_of_rois_src;
+  a.n = (int)n; a.gt_stride = gt_row_stride; a.labels_i64 = labels_are_int64 ? 1 : 0; a.corner = cfg->corner ? 1 : 0;
+  a.beta = cfg->beta;
+  for (int j = 0; j < 7; ++j) a.cw[j] = cfg->code_weights[j];
+  a.w_cls = cfg->cls_weight; a.w_reg = cfg->reg_weight; a.w_corner = cfg->corner_weight;
+  a.out = nullptr; a.d_cls = d_cls; a.d_reg = d_reg; a.reg_targets = reg_targets;
+  hipLaunchKernelGGL(rcnn_loss_frames_kernel, dim3(1), dim3(TPB), 0, (hipStream_t)stream, a, B, loss_frames);
+  CRB_CHECK_LAUNCH();
+  return CRB_OK;
+}
+
+extern "C" int crb_scale_rows_per_frame(const float* src, int64_t rows, int width, int frames, const float* g, float* dst, void* stream) {
+  if (rows < 0 || width <= 0 || frames <= 0 || rows % frames != 0) return CRB_ERR_ARG;
+  if (rows == 0) return CRB_OK;
+  if (!src || !g || !dst) return CRB_ERR_ARG;
+  const int64_t total = rows * width;
+  hipLaunchKernelGGL(scale_rows_kernel, dim3(crb_cdiv(total, 256)), dim3(256), 0, (hipStream_t)stream, src, total, (rows / frames) * width,
+                     g, dst);
   CRB_CHECK_LAUNCH();
   return CRB_OK;
 }

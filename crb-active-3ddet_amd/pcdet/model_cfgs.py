@@ -140,3 +140,20 @@ def pv_rcnn_cfg(kind='kitti'):
                          'SELECT_LABEL_EPOCH_INTERVAL': 40, 'TOTAL_BUDGET_NUMS': 600,
                          'ACTIVE_CONFIG': {'K1': 5, 'K2': 3, 'BANDWIDTH': 5, 'CLUSTERING': 'kmeans++'}},
     })
+
+
+def pv_rcnn_llal_cfg():
+    """values of tools/cfgs/active-kitti_models/pv_rcnn_active_llal.yaml: the KITTI PV-RCNN with the LLAL loss-prediction module
+    (ROI_HEAD.LOSS_NET), no MC-dropout rounds, the loss net frozen during detector training (OPTIMIZATION.LOSS_NET_SKIP) and
+    trained for LOSS_NET_TRAIN_EPOCH epochs per selection round"""
+    c = pv_rcnn_cfg('kitti')
+    h = c.MODEL.ROI_HEAD
+    h.pop('SAMPLING_ROUND')
+    h.LOSS_NET = EasyDict({'SHARED_FC': [256, 256]})
+    h.EMBEDDING_REQUIRED = False
+    c.OPTIMIZATION.NUM_EPOCHS = 60
+    c.OPTIMIZATION.LOSS_NET_SKIP = True
+    c.ACTIVE_TRAIN.METHOD = 'llal'
+    c.ACTIVE_TRAIN.LOSS_NET_TRAIN_EPOCH = 10
+    c.ACTIVE_TRAIN.pop('ACTIVE_CONFIG')
+    return c

@@ -38,6 +38,33 @@ class _PointFocalLoss(torch.autograd.Function):
         return (d * g).view(ctx.pshape), None, None, None, None
 
 
+
+class _PointFocalLossPerFrame(torch.autograd.Function):
+    """reduce=False form: (B,) per-frame losses with the batch-wide positive normaliser (csrc/point_head.hip)"""
+    @staticmethod
+    def forward(ctx, preds, labels, B, alpha, gamma, weight):
+        from crbhip import lib, check, ptr, cur_stream
+        p = preds.contiguous().float()
+        n, C = p.shape
+        buf = torch.empty((B + 1,), dtype=torch.float32, device=p.device)
+        d = torch.empty_like(p)
+        check(lib.crb_point_focal_loss_per_frame(ptr(p), ptr(labels.contiguous()), n, C, B, alpha, gamma, weight, ptr(buf), ptr(d),
+                                                 cur_stream(p.device)), 'crb_point_focal_loss_per_frame')
+        ctx.save_for_backward(d)
+        ctx.pshape, ctx.B = preds.shape, B
+        loss, pos = buf[:B], buf[B]
+        ctx.mark_non_differentiable(pos)
+        ctx.set_materialize_grads(False)
+        return loss, pos
+
+    @staticmethod
+    def backward(ctx, g, _gp):
+        if g is None:
+            return None, None, None, None, None, None
+        from crbhip.rcnn_loss import scale_rows_per_frame
+        (d,) = ctx.saved_tensors
+        return scale_rows_per_frame(d, g, ctx.B).view(ctx.pshape), None, None, None, None, None
+
 class PointHeadTemplate(nn.Module):
     def __init__(self, model_cfg, num_class):
         super().__init__()
@@ -112,6 +139,16 @@ class PointHeadTemplate(nn.Module):
                                               float(self.model_cfg.LOSS_CONFIG.LOSS_WEIGHTS['point_cls_weight']))
             tb_dict = {} if tb_dict is None else tb_dict
             tb_dict.update({'point_loss_cls': loss.detach(), 'point_pos_num': pos})
+            return loss, tb_dict
+        if FUSED and not reduce and preds.is_cuda and type(self.cls_loss_func).__name__ == 'SigmoidFocalClassificationLoss' and \
+                labels.dtype == torch.int64 and preds.shape[1] == 1 and labels.numel() % self.model_cfg.NUM_KEYPOINTS == 0:
+            # (one class: view(-1, NUM_KEYPOINTS).sum(-1) is a per-frame sum; with more it mixes classes, the torch path keeps that)
+            # reduce=False (LLAL loss-net phase): per-frame sums, one launch each way
+            loss, pos = _PointFocalLossPerFrame.apply(preds, labels, labels.numel() // self.model_cfg.NUM_KEYPOINTS,
+                                                      float(self.cls_loss_func.alpha), float(self.cls_loss_func.gamma),
+                                                      float(self.model_cfg.LOSS_CONFIG.LOSS_WEIGHTS['point_cls_weight']))
+            tb_dict = {} if tb_dict is None else tb_dict
+            tb_dict.update({'point_loss_cls': loss[0].detach(), 'point_pos_num': pos})
             return loss, tb_dict
         positives = labels > 0
         cls_weights = ((labels == 0) * 1.0 + 1.0 * positives).float()

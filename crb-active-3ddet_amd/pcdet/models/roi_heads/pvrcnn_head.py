@@ -1,11 +1,13 @@
 """PVRCNNHead (pcdet/models/roi_heads/pvrcnn_head.py:9-242): RoI-grid pooling of keypoint features (HIP ball query +
-grouping), shared FC, class / box branches, MC-dropout passes in eval (SAMPLING_ROUND)."""
+grouping), shared FC, class / box branches, MC-dropout passes in eval (SAMPLING_ROUND), and with ROI_HEAD.LOSS_NET the LLAL
+loss-prediction module on the post-ReLU outputs of the shared FC layers (pvrcnn_head.py:163-180)."""
 import torch
 import torch.nn as nn
 
 from ...ops.pointnet2.pointnet2_stack import pointnet2_modules as pointnet2_stack_modules
 from ...utils import common_utils
 from ...utils.fold_utils import fold_conv_bn
+from .loss_net import LossNet
 from .roi_head_template import RoIHeadTemplate
 
 
@@ -48,7 +50,7 @@ class PVRCNNHead(RoIHeadTemplate):
         self.reg_layers = self.make_fc_layers(input_channels=pre, output_channels=self.box_coder.code_size * self.num_class,
                                               fc_list=self.model_cfg.REG_FC)
         if model_cfg.get('LOSS_NET', None):
-            raise NotImplementedError('LossNet (LLAL baseline) is out of scope, SURVEY §2.1 row 11')
+            self.loss_net = LossNet(model_cfg=model_cfg)
         self.init_weights(weight_init='xavier')
 
     def init_weights(self, weight_init='xavier'):
@@ -62,6 +64,17 @@ class PVRCNNHead(RoIHeadTemplate):
                 if m.bias is not None:
                     nn.init.constant_(m.bias, 0)
         nn.init.normal_(self.reg_layers[-1].weight, mean=0, std=0.001)
+
+    def predict_loss(self, latents, batch_size):
+        """LossNet on the ReLU outputs of the shared FC layers -> (B, 1). Runs on every forward, also while the module is frozen
+        (OPTIMIZATION.LOSS_NET_SKIP): its BatchNorm layers update their running statistics in train mode like the reference's."""
+        rows = latents[0].shape[0]
+        per = self.loss_net.rows_per_frame
+        if rows != batch_size * per:
+            raise ValueError('ROI_HEAD.LOSS_NET needs exactly TARGET_CONFIG.ROI_PER_IMAGE = %d RoIs per frame, got %d rows for %d '
+                             'frames (in eval the RoI count per frame is NMS_CONFIG.TEST.NMS_POST_MAXSIZE = %d)' %
+                             (per, rows, batch_size, self.model_cfg.NMS_CONFIG.TEST.NMS_POST_MAXSIZE))
+        return self.loss_net(latents, batch_size=batch_size)
 
     def roi_grid_pool(self, batch_dict):
         """rois (B,N,7), keypoints -> (B*N, G^3, C)"""
@@ -108,34 +121,44 @@ class PVRCNNHead(RoIHeadTemplate):
     # (28 MB, differentiable) leaves the pooled rows where the pooling wrote them: same products, another K order in the GEMM.
     WEIGHT_SIDE_FLATTEN = __import__('os').environ.get('CRB_ROI_WEIGHT_SIDE_FLATTEN', '1') == '1'
 
-    def _heads_pooled(self, pooled):
-        """pooled (BN, G^3, C) -> shared, rcnn_cls, rcnn_reg without the channel-major copy of the pooled tensor"""
+    def _heads_pooled(self, pooled, taps=None):
+        """pooled (BN, G^3, C) -> shared, rcnn_cls, rcnn_reg without the channel-major copy of the pooled tensor; `taps` (a list)
+        receives the output of every ReLU of shared_fc_layer (the LossNet latents)"""
         mods = list(self.shared_fc_layer)
         n, g3, c = pooled.shape
         conv0 = mods[0]
         if not (self.WEIGHT_SIDE_FLATTEN and isinstance(conv0, nn.Conv1d) and conv0.kernel_size == (1,) and
                 conv0.in_channels == g3 * c):
-            return self._heads(pooled.permute(0, 2, 1).contiguous().view(n, -1, 1))
+            return self._heads(pooled.permute(0, 2, 1).contiguous().view(n, -1, 1), taps)
         w = conv0.weight.view(conv0.out_channels, c, g3).permute(0, 2, 1).reshape(conv0.out_channels, g3 * c)
         x = torch.nn.functional.linear(pooled.reshape(n, g3 * c), w, conv0.bias).unsqueeze(-1)     # (BN, 256, 1)
         for m in mods[1:]:
             x = m(x)
+            if taps is not None and isinstance(m, nn.ReLU):
+                taps.append(x)
         shared = x
         rcnn_cls = self.cls_layers(shared).transpose(1, 2).contiguous().squeeze(dim=1)
         rcnn_reg = self.reg_layers(shared).transpose(1, 2).contiguous().squeeze(dim=1)
         return shared, rcnn_cls, rcnn_reg
 
-    def _heads(self, pooled_flat):
-        shared = self.shared_fc_layer(pooled_flat)
+    def _heads(self, pooled_flat, taps=None):
+        if taps is None:
+            shared = self.shared_fc_layer(pooled_flat)
+        else:
+            shared = pooled_flat
+            for m in self.shared_fc_layer:
+                shared = m(shared)
+                if isinstance(m, nn.ReLU):
+                    taps.append(shared)
         rcnn_cls = self.cls_layers(shared).transpose(1, 2).contiguous().squeeze(dim=1)
         rcnn_reg = self.reg_layers(shared).transpose(1, 2).contiguous().squeeze(dim=1)
         return shared, rcnn_cls, rcnn_reg
 
     # ---- inference fast path (same values up to f32 rounding) -------------------------------------------------------
     @staticmethod
-    def _run_folded(mods, x):
+    def _run_folded(mods, x, taps=None):
         """Conv1d(k=1) -> BatchNorm1d(eval) pairs as one folded conv; ReLU / Dropout modules run as they are (Dropout
-        stays stochastic when the CRB strategy switched it to train mode)"""
+        stays stochastic when the CRB strategy switched it to train mode); `taps` receives every ReLU output"""
         i = 0
         while i < len(mods):
             m = mods[i]
@@ -156,17 +179,21 @@ class PVRCNNHead(RoIHeadTemplate):
                 i += 1
             else:
                 x = m(x)
+                if taps is not None and isinstance(m, nn.ReLU):
+                    taps.append(x)
                 i += 1
         return x
 
-    def _heads_eval(self, pooled, rounds):
+    def _heads_eval(self, pooled, rounds, taps=None):
         """MC-dropout passes of pvrcnn_head.py:187-202 on pooled (BN, G^3, C) features.
         * Everything before the first Dropout of shared_fc_layer is deterministic in eval mode, so the 27648->256 layer
           (7 M MACs per RoI) runs once instead of `rounds` times. Its weight is re-ordered once (cached) from the reference's
           channel-major flattening (c*G^3 + g) to the pooled tensor's own (g*C + c) order: no permute().contiguous() copy of
           the 226 MB pooled tensor.
         * The `rounds` passes only differ by their dropout masks: they run as ONE batch of rounds*BN rows through the
-          remaining layers (independent masks per row and element, as in `rounds` separate calls)."""
+          remaining layers (independent masks per row and element, as in `rounds` separate calls).
+        * `taps` receives the ReLU outputs of the first pass (the LossNet latents): the deterministic prefix and the rows of pass 0
+          of the remaining layers, no extra FC pass."""
         mods = list(self.shared_fc_layer)
         first_dp = next((k for k, m in enumerate(mods) if isinstance(m, nn.Dropout)), len(mods))
         n, g3, c = pooled.shape
@@ -174,12 +201,15 @@ class PVRCNNHead(RoIHeadTemplate):
         if isinstance(conv0, nn.Conv1d) and isinstance(bn0, nn.BatchNorm1d) and conv0.in_channels == g3 * c:
             w0, b0 = fold_conv_bn(conv0, bn0, _gc_order(c, g3))
             x = torch.addmm(b0, pooled.reshape(n, g3 * c), w0.t()).unsqueeze(-1)           # (BN, 256, 1)
-            prefix = self._run_folded(mods[2:first_dp], x)
+            prefix = self._run_folded(mods[2:first_dp], x, taps)
         else:
-            prefix = self._run_folded(mods[:first_dp], pooled.permute(0, 2, 1).contiguous().view(n, -1, 1))
+            prefix = self._run_folded(mods[:first_dp], pooled.permute(0, 2, 1).contiguous().view(n, -1, 1), taps)
         r = max(1, rounds)
         stacked = prefix.repeat(r, 1, 1) if r > 1 else prefix                             # (r*BN, 256, 1)
-        shared = self._run_folded(mods[first_dp:], stacked)
+        later = [] if taps is not None else None
+        shared = self._run_folded(mods[first_dp:], stacked, later)
+        if taps is not None:
+            taps.extend(t if r == 1 else t[:n] for t in later)
         rcnn_cls = self._run_folded(list(self.cls_layers), shared).transpose(1, 2).contiguous().squeeze(dim=1)
         rcnn_reg = self._run_folded(list(self.reg_layers), shared).transpose(1, 2).contiguous().squeeze(dim=1)
         return [(shared[k * n:(k + 1) * n], rcnn_cls[k * n:(k + 1) * n], rcnn_reg[k * n:(k + 1) * n]) for k in range(r)]
@@ -195,19 +225,21 @@ class PVRCNNHead(RoIHeadTemplate):
             batch_dict['roi_labels'] = targets_dict['roi_labels']
         pooled = self.roi_grid_pool(batch_dict)                                   # (BN, G^3, C)
         n = pooled.shape[0]
+        taps = [] if hasattr(self, 'loss_net') else None
         fast = (not self.training) and (not torch.is_grad_enabled()) and \
             not any(m.training for m in self.modules() if isinstance(m, nn.BatchNorm1d))
         # the reference's channel-major flattening (a 226 MB copy at bs=16) is only needed off the fast path
         pooled_flat = None
         if fast:
             rounds = self.model_cfg.get('SAMPLING_ROUND', None) or 1
-            passes = self._heads_eval(pooled, rounds)
+            passes = self._heads_eval(pooled, rounds, taps)
             shared, rcnn_cls, rcnn_reg = passes[-1]
         elif self.training:
-            shared, rcnn_cls, rcnn_reg = self._heads_pooled(pooled)
+            shared, rcnn_cls, rcnn_reg = self._heads_pooled(pooled, taps)
         else:
             pooled_flat = pooled.permute(0, 2, 1).contiguous().view(n, -1, 1)                        # (BN, C*G^3, 1)
-            shared, rcnn_cls, rcnn_reg = self._heads(pooled_flat)
+            shared, rcnn_cls, rcnn_reg = self._heads(pooled_flat, taps)
+        loss_predictions = self.predict_loss(taps, batch_dict['batch_size']) if taps is not None else None
         if not self.training:
             rounds = self.model_cfg.get('SAMPLING_ROUND', None)
             if rounds:
@@ -228,7 +260,11 @@ class PVRCNNHead(RoIHeadTemplate):
             batch_dict['batch_cls_preds'] = batch_cls_preds
             batch_dict['batch_box_preds'] = batch_box_preds
             batch_dict['cls_preds_normalized'] = False
+            if loss_predictions is not None:
+                batch_dict['loss_predictions'] = loss_predictions
         else:
+            if loss_predictions is not None:
+                targets_dict['loss_predictions'] = loss_predictions
             targets_dict['rcnn_cls'] = rcnn_cls
             targets_dict['rcnn_reg'] = rcnn_reg
             self.forward_ret_dict = targets_dict

@@ -201,10 +201,10 @@ class RoIHeadTemplate(nn.Module):
         return loss, {'rcnn_loss_cls': (loss if reduce else loss[0]).detach()}
 
     def _fused_loss_cfg(self, reduce):
-        """the configuration crb_rcnn_loss implements (BinaryCrossEntropy, smooth-l1 (+ corner), code size 7, the whole-batch
-        reduction, not the CRB branch) -> CrbRcnnLossCfg or None"""
+        """the configuration crb_rcnn_loss / crb_rcnn_loss_per_frame implement (BinaryCrossEntropy, smooth-l1 (+ corner), code
+        size 7, not the CRB branch) -> CrbRcnnLossCfg or None"""
         loss_cfgs, ret = self.model_cfg.LOSS_CONFIG, self.forward_ret_dict
-        if not (FUSED_LOSS and reduce) or 'reg_sample_targets' in ret or not ret['rcnn_reg'].is_cuda or \
+        if not FUSED_LOSS or 'reg_sample_targets' in ret or not ret['rcnn_reg'].is_cuda or \
                 loss_cfgs.CLS_LOSS != 'BinaryCrossEntropy' or loss_cfgs.REG_LOSS != 'smooth-l1' or self.box_coder.code_size != 7 or \
                 getattr(self.box_coder, 'encode_angle_by_sincos', False) or ret['rcnn_reg'].shape[-1] != 7 or \
                 ret['rcnn_cls'].numel() != ret['rcnn_reg'].shape[0] or self.reg_loss_func.code_weights is None:
@@ -221,6 +221,17 @@ class RoIHeadTemplate(nn.Module):
     def get_loss(self, tb_dict=None, reduce=True):
         tb_dict = {} if tb_dict is None else tb_dict
         cfg = self._fused_loss_cfg(reduce)
+        if cfg is not None and not reduce:
+            # reduce=False (LLAL loss-net phase): per-frame losses with the reference's denominators, one launch each way
+            from crbhip import rcnn_loss
+            ret = self.forward_ret_dict
+            total, parts, ret['rcnn_reg_gt'] = rcnn_loss.rcnn_loss_per_frame(
+                ret['rcnn_cls'], ret['rcnn_reg'], ret['rcnn_cls_labels'], ret['reg_valid_mask'], ret['rois'], ret['gt_of_rois'],
+                ret['gt_of_rois_src'], cfg)
+            tb_dict.update({'rcnn_loss_cls': parts[0, 0], 'rcnn_loss_reg': parts[0, 1], 'rcnn_loss': parts[0, 3]})
+            if cfg.corner:
+                tb_dict['rcnn_loss_corner'] = parts[0, 2]
+            return total, tb_dict
         if cfg is not None:
             from crbhip import rcnn_loss
             ret = self.forward_ret_dict
@@ -238,6 +249,30 @@ class RoIHeadTemplate(nn.Module):
         rcnn_loss = loss_cls + loss_reg
         tb_dict['rcnn_loss'] = (rcnn_loss if reduce else rcnn_loss[0]).detach()
         return rcnn_loss, tb_dict
+
+    @staticmethod
+    def LossPredLoss(input, target, margin=1.0, reduction='mean'):
+        """ranking loss of LLAL (roi_head_template.py:289-311): frame i is paired with frame B-1-i, the sign of the true loss
+        difference is the target. Kept as the reference writes it, including its broadcast of the (B/2,) signs against the
+        (B/2, 1) prediction differences: the 'mean' is the sum over that (B/2, B/2) product divided by B/2."""
+        assert len(input) % 2 == 0, 'the batch size is not even.'
+        assert input.shape == input.flip(0).shape
+        input = (input - input.flip(0))[:len(input) // 2]
+        target = (target - target.flip(0))[:len(target) // 2]
+        target = target.detach()
+        one = 2 * torch.sign(torch.clamp(target, min=0)) - 1
+        if reduction == 'mean':
+            return torch.sum(torch.clamp(margin - one * input, min=0)) / input.size(0)
+        if reduction == 'none':
+            return torch.clamp(margin - one * input, min=0)
+        raise NotImplementedError(reduction)
+
+    def get_loss_loss_net(self, tb_dict=None, loss=None):
+        """LossPredLoss of the loss predictions of this step against the per-frame detector losses `loss` (B,)"""
+        tb_dict = {} if tb_dict is None else tb_dict
+        loss_loss_net = self.LossPredLoss(self.forward_ret_dict['loss_predictions'], loss)
+        tb_dict['loss_loss_net'] = loss_loss_net.detach()
+        return loss_loss_net
 
     def generate_predicted_boxes(self, batch_size, rois, cls_preds, box_preds):
         """rois (B,N,7), cls (BN,C), box (BN,code) -> (B,N,C), (B,N,code) in LiDAR coordinates"""

@@ -1,11 +1,13 @@
-"""pcdet.query_strategies factory (pcdet/query_strategies/__init__.py:12-29). `llal` needs the loss-prediction module of
-the LLAL detector variant (`pv_rcnn_llal`, not on the SECOND / PV-RCNN / CRB path) and is not provided."""
+"""pcdet.query_strategies factory (pcdet/query_strategies/__init__.py:12-29): the reference's eight strategies plus the
+unregistered `bald`. `llal` needs the loss-prediction module of the LLAL detector variant (ROI_HEAD.LOSS_NET,
+pcdet.model_cfgs.pv_rcnn_llal_cfg)."""
 from .badge_sampling import BadgeSampling
 from .bald_sampling import BALDSampling
 from .confidence_sampling import ConfidenceSampling
 from .coreset_sampling import CoresetSampling
 from .crb_sampling import CRBSampling
 from .entropy_sampling import EntropySampling
+from .llal_sampling import LLALSampling
 from .montecarlo_sampling import MonteCarloSampling
 from .random_sampling import RandomSampling
 from .strategy import Strategy  # noqa: F401
@@ -19,6 +21,7 @@ __factory = {
     'coreset': CoresetSampling,
     'badge': BadgeSampling,
     'crb': CRBSampling,
+    'llal': LLALSampling,
 }
 
 

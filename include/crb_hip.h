@@ -657,6 +657,13 @@ int crb_point_labels(const int32_t* inner, const int32_t* outer, const float* gt
                      int num_class, int64_t* labels, void* stream);
 int crb_point_focal_loss(const float* preds, const int64_t* labels, int64_t n, int num_class, float alpha, float gamma,
                          float loss_weight, float* loss, float* d_preds, void* stream);
+/* crb_point_focal_loss_per_frame replaces the reduce=False form of the same loss (point_head_template.py:131-155,
+ *   src.view(-1, NUM_KEYPOINTS).sum(-1), ~25 torch launches forward and backward): n = B * points per frame -> loss (B + 1) =
+ *   {per-frame point_loss_cls (x loss_weight, normalised by the WHOLE batch's max(positives, 1)), positives}; d_preds (n, num_class)
+ *   = d loss[frame] / d preds for that frame's rows (a unit upstream value per frame; crb_scale_rows_per_frame applies the real one).
+ *   One workgroup, frames in order, sums in a fixed order. */
+int crb_point_focal_loss_per_frame(const float* preds, const int64_t* labels, int64_t n, int num_class, int B, float alpha, float gamma,
+                                   float loss_weight, float* loss, float* d_preds, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * a22 / a24  second-stage losses and the canonical transformation of the sampled ground truths (csrc/rcnn_loss.hip)
@@ -685,6 +692,19 @@ int crb_rcnn_loss(const float* rcnn_cls, const float* rcnn_reg, const void* cls_
                   const int64_t* reg_valid_mask, const float* rois, const float* gt_of_rois, const float* gt_of_rois_src,
                   int gt_row_stride, int64_t n, const CrbRcnnLossCfg* cfg, float* loss, float* d_cls, float* d_reg,
                   float* reg_targets, void* stream);
+/* crb_rcnn_loss_per_frame replaces the reduce=False form of get_box_cls_layer_loss / get_box_reg_layer_loss (roi_head_template.py:
+ *   142-285 with reduce=False, the LLAL loss-net phase; ~270 torch launches forward and backward): n = B * ROI_PER_IMAGE RoIs, same
+ *   inputs as crb_rcnn_loss -> loss_frames (B, 4) = {rcnn_loss_cls, rcnn_loss_reg, rcnn_loss_corner, rcnn_loss} per frame, cls and
+ *   reg divided by the WHOLE batch's valid / foreground counts, corner by the FRAME's foreground count (the reference's quirks);
+ *   d_cls (n), d_reg (n,7) = d loss_frames[frame, 3] / d (rcnn_cls, rcnn_reg) for that frame's rows (unit upstream per frame).
+ *   One workgroup, frames in order, sums in a fixed order. */
+int crb_rcnn_loss_per_frame(const float* rcnn_cls, const float* rcnn_reg, const void* cls_labels, int labels_are_int64,
+                            const int64_t* reg_valid_mask, const float* rois, const float* gt_of_rois, const float* gt_of_rois_src,
+                            int gt_row_stride, int64_t n, int B, const CrbRcnnLossCfg* cfg, float* loss_frames, float* d_cls, float* d_reg,
+                            float* reg_targets, void* stream);
+/* backward of the per-frame losses above (replaces autograd's broadcast multiply of the per-row gradients by the (B,) upstream
+ * gradient): src (rows, width) -> dst = src * g[row / (rows / frames)]. */
+int crb_scale_rows_per_frame(const float* src, int64_t rows, int width, int frames, const float* g, float* dst, void* stream);
 int crb_roi_canonical_targets(const float* rois, int roi_row_stride, const float* gt_of_rois, int gt_row_stride, int64_t n,
                               float* out, void* stream);
 /* grid points of the RoI-grid pooling (PVRCNNHead.get_global_grid_points_of_roi + get_dense_grid_points, pvrcnn_head.py:116-141):
@@ -841,6 +861,48 @@ int crb_bev_interpolate_forward(const float* bev, int B, int H, int W, int C, co
                                 float y_min, float voxel_x, float voxel_y, float bev_stride, float* out, void* stream);
 int crb_bev_interpolate_backward(const float* dout, int B, int H, int W, int C, const float* keypoints, int64_t M, float x_min,
                                  float y_min, float voxel_x, float voxel_y, float bev_stride, float* dbev, void* stream);
+
+/* LLAL loss-prediction module (csrc/loss_net.hip)
+ * replaces: LossNet.forward (pcdet/models/roi_heads/loss_net.py:54-70) and its autograd: per shared-FC layer k a Conv1d(C_k -> 1,
+ *           k=1, bias=False) over the R = frames * rows_per_frame RoI rows, BatchNorm1d(1) (train mode: batch statistics over the R
+ *           rows, running_mean / running_var updated with `momentum` and the unbiased variance, num_batches_tracked += 1; eval mode:
+ *           the running statistics), ReLU, view(frames, rows_per_frame), cat over k, Linear(num_layer * rows_per_frame -> 1).
+ *           ~12 torch launches each way per layer.
+ * x[k] (R, channels[k]) f32 row-major: the post-ReLU output of shared FC layer k (pvrcnn_head.py:163-176); w[k] (channels[k]) the
+ * conv weight; gamma / beta / running_mean / running_var (1) and num_batches_tracked (1) i64 of bn_k; lin_w (num_layer *
+ * rows_per_frame), lin_b (1) -> out (frames) f32. Accumulation in f64, every sum in a fixed order, no atomics: bit-reproducible.
+ * crb_lossnet_forward: two launches. ws (crb_lossnet_workspace_bytes) keeps what the backward reads; hand the same ws to it.
+ * crb_lossnet_backward: two launches. d_out (frames) upstream gradient -> d_x[k] (R, channels[k]) (NULL: not formed), d_w[k]
+ * (channels[k]), d_gamma_beta (2 * num_layer: gamma_k at 2k, beta_k at 2k + 1), d_lin_w, d_lin_b (1); all written, none added to.
+ * ---------------------------------------------------------------------------------------------- */
+#define CRB_LOSSNET_MAX_LAYERS 4
+typedef struct CrbLossNetArgs {
+  const float* x[CRB_LOSSNET_MAX_LAYERS];
+  const float* w[CRB_LOSSNET_MAX_LAYERS];
+  const float* gamma[CRB_LOSSNET_MAX_LAYERS];
+  const float* beta[CRB_LOSSNET_MAX_LAYERS];
+  float* running_mean[CRB_LOSSNET_MAX_LAYERS];
+  float* running_var[CRB_LOSSNET_MAX_LAYERS];
+  int64_t* num_batches_tracked[CRB_LOSSNET_MAX_LAYERS];
+  int32_t channels[CRB_LOSSNET_MAX_LAYERS];
+  int32_t num_layer;             /* 1 .. CRB_LOSSNET_MAX_LAYERS */
+  int32_t rows_per_frame;        /* TARGET_CONFIG.ROI_PER_IMAGE */
+  int32_t frames;                /* batch size */
+  int32_t training;              /* 1: batch statistics + running-statistics update; 0: running statistics */
+  float momentum, eps;           /* bn_k.momentum (not None), bn_k.eps */
+} CrbLossNetArgs;
+typedef struct CrbLossNetGrads {
+  float* d_x[CRB_LOSSNET_MAX_LAYERS];
+  float* d_w[CRB_LOSSNET_MAX_LAYERS];
+  float* d_gamma_beta;
+  float* d_lin_w;
+  float* d_lin_b;
+} CrbLossNetGrads;
+int64_t crb_lossnet_workspace_bytes(int num_layer, int64_t rows);
+int crb_lossnet_forward(const CrbLossNetArgs* args, const float* lin_w, const float* lin_b, float* out, void* ws, int64_t ws_bytes,
+                        void* stream);
+int crb_lossnet_backward(const CrbLossNetArgs* args, const float* lin_w, const float* d_out, void* ws, int64_t ws_bytes,
+                         const CrbLossNetGrads* grads, void* stream);
 
 #ifdef __cplusplus
 }
