@@ -5,7 +5,8 @@ convolution; MIOpen's implicit GEMM: 1.2e-6).
 Kernels: forward and input gradient run on the round-6 split-bf16 kernel (crb_conv3x3_winograd4_nhwc; KERNEL below) where it has
 an instance, otherwise on the round-4 f32-MFMA design (crb_conv3x3_winograd2_nhwc; 0.71 ms per 128->128 @ 16x200x176 call against
 MIOpen's 1.41), which also is what the `*2` names meant before round 6; the BEV backbone calls — `conv3x3` (training: forward + input gradient) and `fold` / `conv3x3_U2`
-(inference: BatchNorm folded, bias + ReLU in the epilogue); the round-3 kernel (crb_conv3x3_winograd_nhwc, 1.15 ms) stays for
+(inference: BatchNorm folded, bias + ReLU in the epilogue); the weight gradient runs on the split-bf16 kernel as well
+(crb_winograd4_wgrad; WGRAD_KERNEL below) where Cin and Cout are multiples of 128, otherwise on crb_winograd2_wgrad; the round-3 kernel (crb_conv3x3_winograd_nhwc, 1.15 ms) stays for
 A/B runs in tools/."""
 import torch
 
@@ -14,7 +15,7 @@ from ._lib import lib, check, ptr, cur_stream, require_cuda, CrbHipError
 
 # When set to a list, every Winograd launch appends (kind, cin, cout, N, H, W, ev0, ev1) with HIP events on the launch stream
 # (torch's current stream IS the stream handed to the C-ABI); bench.py reads them for the roofline / kernel table.
-# kind: 'wino_conv' (forward and input gradient: the same kernel) | 'wino_wgrad' (both launches of crb_winograd2_wgrad)
+# kind: 'wino_conv' (forward and input gradient: the same kernel) | 'wino_wgrad' (both launches of crb_winograd4_wgrad / crb_winograd2_wgrad)
 PROFILE = None
 
 
@@ -79,7 +80,7 @@ def transform_weights2(g):
 # Which kernel runs the forward / input-gradient convolutions: 'x6' = csrc/winograd_conv4.hip (the 16 GEMMs as six bf16 MFMA passes over an
 # exact three-way split of the f32 operands: f32 in, f32 out, errors against f64 at the f32-MFMA kernel's level, ~11 % faster), 'f32' =
 # csrc/winograd_conv2.hip (exact-f32 MFMA). 'x6' needs Cin % 16 == 0, Cout % 64 == 0 and maps of at least 31 rows; everything else
-# (and everything under CRB_WINOGRAD_KERNEL=f32) runs on the f32-MFMA kernel. The weight gradient is the f32-MFMA kernel's either way.
+# (and everything under CRB_WINOGRAD_KERNEL=f32) runs on the f32-MFMA kernel. The weight gradient has its own choice: WGRAD_KERNEL below.
 KERNEL = __import__('os').environ.get('CRB_WINOGRAD_KERNEL', 'x6')
 
 
@@ -319,8 +320,19 @@ def conv3x3_U(x, U, bias=None, relu=False):
     return y
 
 
+# Which kernel runs the weight gradient: 'x6' = csrc/winograd_wgrad4.hip (both transformed operands split three ways, six bf16 MFMA
+# passes per product, f32 in / f32 out, errors against f64 at the f32-MFMA kernel's level) wherever it has an instance (what
+# crb_winograd4_wgrad_supported answers: Cin % 128 == 0 and Cout % 128 == 0), 'f32' = csrc/winograd_wgrad.hip everywhere (the tests'
+# reference runs and A/B). Shapes without an 'x6' instance run on the f32-MFMA kernel either way.
+WGRAD_KERNEL = __import__('os').environ.get('CRB_WINOGRAD_WGRAD_KERNEL', 'x6')
+
+
+def _use_wgrad4(cin, cout, H, W):
+    return WGRAD_KERNEL == 'x6' and bool(lib.crb_winograd4_wgrad_supported(int(cin), int(cout), int(H), int(W)))
+
+
 def wgrad_supported(cin, cout, H, W):
-    return bool(lib.crb_winograd2_wgrad_supported(int(cin), int(cout), int(H), int(W)))
+    return _use_wgrad4(cin, cout, H, W) or bool(lib.crb_winograd2_wgrad_supported(int(cin), int(cout), int(H), int(W)))
 
 
 _WGRAD_WS = {}
@@ -328,7 +340,8 @@ _WGRAD_WS = {}
 
 def conv3x3_wgrad(x, dy, like):
     """x (N,Cin,H,W), dy (N,Cout,H,W) f32 channels_last -> gradient of the nn.Conv2d weight (Cout,Cin,3,3) in the memory layout
-    of `like` (crb_winograd2_wgrad: both operands transformed inside the kernel, dW = G^T dU G)"""
+    of `like` (crb_winograd4_wgrad where it has an instance, else crb_winograd2_wgrad: both operands transformed inside the kernel,
+    dW = G^T dU G)"""
     require_cuda(x, dy)
     xv, gv = _nhwc(x.float()), _nhwc(dy.float())
     N, H, W, cin = xv.shape
@@ -336,15 +349,18 @@ def conv3x3_wgrad(x, dy, like):
     if gv.shape[:3] != xv.shape[:3] or not wgrad_supported(cin, cout, H, W):
         raise CrbHipError('no Winograd weight-gradient instance for %d -> %d channels' % (cin, cout))
     dw = torch.empty_like(like, dtype=torch.float32)
-    nbytes = int(lib.crb_winograd2_wgrad_workspace_bytes(cin, cout))
+    four = _use_wgrad4(cin, cout, H, W)
+    # sized by the larger of the two kernels' answers: switching kernels inside one process does not reallocate
+    nbytes = max(int(lib.crb_winograd4_wgrad_workspace_bytes(cin, cout)), int(lib.crb_winograd2_wgrad_workspace_bytes(cin, cout)))
     key = (x.device, torch.cuda.current_stream(x.device).cuda_stream)
     ws = _WGRAD_WS.get(key)                      # one per (device, stream): every call on a stream is ordered behind the last
     if ws is None or ws.numel() * 4 < nbytes:
         ws = _WGRAD_WS[key] = torch.empty((nbytes // 4,), dtype=torch.float32, device=x.device)
     so, si, sky, skx = dw.stride()
     e0 = _prof_begin()
-    check(lib.crb_winograd2_wgrad(xv.data_ptr(), gv.data_ptr(), dw.data_ptr(), so, si, sky, skx, N, H, W, cin, cout, ptr(ws),
-                                  ws.numel() * 4, cur_stream(x.device)), 'crb_winograd2_wgrad')
+    fn, name = (lib.crb_winograd4_wgrad, 'crb_winograd4_wgrad') if four else (lib.crb_winograd2_wgrad, 'crb_winograd2_wgrad')
+    check(fn(xv.data_ptr(), gv.data_ptr(), dw.data_ptr(), so, si, sky, skx, N, H, W, cin, cout, ptr(ws), ws.numel() * 4,
+             cur_stream(x.device)), name)
     _prof_end(e0, 'wino_wgrad', cin, cout, N, H, W)
     return dw
 
@@ -382,7 +398,8 @@ WGRAD = __import__('os').environ.get('CRB_WINOGRAD_WGRAD', '1') != '0'      # 0:
 
 def conv3x3(x, weight, bias=None):
     """differentiable 3x3 stride-1 pad-1 convolution: forward, input gradient and weight gradient on the Winograd kernels
-    (weight gradient on MIOpen where crb_winograd2_wgrad has no instance: channel counts not multiples of 64).
+    (weight gradient on MIOpen where neither crb_winograd4_wgrad nor crb_winograd2_wgrad has an instance: channel counts not
+    multiples of 64).
     Callers check `supported2(Cin, Cout, H, W)` first."""
     return _Conv3x3.apply(x, weight, bias)
 

@@ -32,14 +32,12 @@
 #include <atomic>
 #include <type_traits>
 #include "crb_common.h"
+#include "winograd_split.h"      // split3 and the bf16 / u32 vector types (shared with winograd_wgrad4.hip)
 #include "../../include/crb_hip.h"
 
 typedef float f32x2 __attribute__((ext_vector_type(2)));
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 
 namespace {
 
@@ -67,16 +65,7 @@ __device__ unsigned long long* g_wino4_dbg = nullptr;      // measurement mode 9
 #endif
 __global__ void cu_busy4_set_kernel(int v) { __hip_atomic_store(&g_cu_busy4, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
 
-// exact three-way split: the bf16 bit patterns (high halves) of x1, x2, x3
-__device__ __forceinline__ void split3(float x, unsigned& h1, unsigned& h2, unsigned& h3) {
-  const unsigned b = __float_as_uint(x);
-  const float r1 = x - __uint_as_float(b & 0xffff0000u);
-  const unsigned b1 = __float_as_uint(r1);
-  const float r2 = r1 - __uint_as_float(b1 & 0xffff0000u);
-  h1 = b >> 16;
-  h2 = b1 >> 16;
-  h3 = __float_as_uint(r2) >> 16;
-}
+// (split3, the exact three-way split: winograd_split.h)
 
 // ---- weight image. Byte offset of (xi = 4 i + jx, piece p, kernel input channel ci, kernel output channel co):
 //      [co / 64][ci / 16][i][jx][p][k group (ci % 16) / 8][row co % 64][element ci % 8] bf16  - a phase image is one linear 24 KB copy

@@ -837,6 +837,20 @@ int crb_winograd2_wgrad_supported(int cin, int cout, int H, int W);
 int64_t crb_winograd2_wgrad_workspace_bytes(int cin, int cout);
 int crb_winograd2_wgrad(const float* x, const float* dy, float* dw, int64_t so, int64_t si, int64_t sky, int64_t skx,
                         int N, int H, int W, int cin, int cout, void* workspace, int64_t workspace_bytes, void* stream);
+/* The same weight gradient on the bf16 matrix pipe (csrc/winograd_wgrad4.hip): V = B^T d B and M = A dY A^T are formed in f32 with the
+ * additions of crb_winograd2_wgrad, each is written as the exact sum of three bf16 values (the split of crb_conv3x3_winograd4_nhwc) and
+ * every product runs as six bf16 MFMA passes with f32 accumulation; partials per range of tiles, summed in range order in double,
+ * dW = G^T dU G in double: bit-reproducible, errors against f64 at the level of crb_winograd2_wgrad's. An Inf in x or dy turns the
+ * entries it reaches into NaN (inf - inf in the split), values below 2^-110 lose their low pieces to flushing.
+ * replaces: crb_winograd2_wgrad (v_mfma_f32_16x16x4_f32 runs at the f32 vector rate) where it has an instance, and through it
+ *           aten.convolution_backward(..., output_mask = [False, True, False]) for torch.nn.Conv2d(C, C, 3, padding=1) of
+ *           pcdet/models/backbones_2d/base_bev_backbone.py:24-41.
+ * Same arguments as the crb_winograd2_wgrad trio. Instances: Cin % 128 == 0, Cout % 128 == 0, both <= 1024 (a workgroup owns one xi
+ * row x 128 x 128 channels); everything else stays on crb_winograd2_wgrad. */
+int crb_winograd4_wgrad_supported(int cin, int cout, int H, int W);
+int64_t crb_winograd4_wgrad_workspace_bytes(int cin, int cout);
+int crb_winograd4_wgrad(const float* x, const float* dy, float* dw, int64_t so, int64_t si, int64_t sky, int64_t skx,
+                        int N, int H, int W, int cin, int cout, void* workspace, int64_t workspace_bytes, void* stream);
 
 /* Scheduling hint, no reference counterpart: PV-RCNN's keypoint sampling (crb_furthest_point_sampling_stack on a side stream under
  * the backbones) holds one CU per frame for ~5 ms while the persistent one-workgroup-per-CU Winograd launches of the BEV backbone

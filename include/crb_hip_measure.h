@@ -34,6 +34,10 @@ int crb_winograd2_set_debug(void* dev_buf_u64x16_per_wg);
 int crb_winograd2_set_persistent(int on);
 /* measurement builds of the Winograd weight gradient (wrong results): 1 = no MFMAs, 2 = no transforms, 3 = no DMA / gradient loads in the loop */
 int crb_winograd2_wgrad_set_mode(int mode);
+/* measurement builds of the split-bf16 Winograd weight gradient (crb_winograd4_wgrad; wrong results): 1 = no MFMAs, 2 = no transforms
+ * (operand images never written), 3 = no map loads; A/B builds with correct results: 4 = with prefetch touches of the chunk after
+ * next (at 2 loads per gap), 5 / 6 = 2 / 5 pixel loads per MFMA gap instead of 1.5; 0 = the product kernel */
+int crb_winograd4_wgrad_set_mode(int mode);
 /* measurement builds of crb_tables_finish's chunk pass (wrong tables by design): bit 0 = no sort, bit 1 = no packed-index fill,
  * bit 2 = no pair lists */
 int crb_tables_set_skip(int bits);
