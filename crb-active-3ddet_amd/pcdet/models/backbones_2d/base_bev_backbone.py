@@ -1,5 +1,6 @@
 """BaseBEVBackbone (pcdet/models/backbones_2d/base_bev_backbone.py:6-112): dense 2-D convs. Same module tree => same
-state_dict keys. The stride-1 3x3 convolutions run on the hand-written Winograd kernel (below), the rest on MIOpen."""
+state_dict keys. The stride-1 3x3 convolutions run on the hand-written Winograd kernel (below), the kernel = stride up-sampling
+branches on the split-bf16 row-GEMM kernels (crbhip.rows_gemm, csrc/rows_gemm4.hip), the rest on MIOpen."""
 import numpy as np
 import torch
 import torch.nn as nn
@@ -196,7 +197,15 @@ class BaseBEVBackbone(nn.Module):
     @staticmethod
     def _up(conv, x):
         """first module of an up-sampling branch. A kernel-1 stride-1 ConvTranspose2d / Conv2d without bias on a
-        channels_last CUDA map is the GEMM rows @ W (no convolution kernel); everything else runs as the module."""
+        channels_last CUDA map is the GEMM rows @ W (no convolution kernel); everything else runs as the module.
+        Kernel = stride ConvTranspose2d layers (1 or 2) run on the split-bf16 row-GEMM kernels (crbhip.rows_gemm) where they have an
+        instance; CRB_ROWS_GEMM_KERNEL=vendor gives the paths below back. In the deterministic mode the stride-2 branch keeps
+        dense_strided's weight gradient; its forward and input gradient are the default mode's (rows_gemm.up_conv)."""
+        if ROWS_GEMM and x.is_cuda:
+            from crbhip import rows_gemm
+            y = rows_gemm.up_conv(conv, x)
+            if y is not None:
+                return y
         if ROWS_GEMM and x.is_cuda and conv.bias is None and conv.kernel_size == (1, 1) and conv.stride == (1, 1) and \
                 conv.padding == (0, 0) and conv.groups == 1 and conv.dilation == (1, 1):
             rows = rows_view(x)

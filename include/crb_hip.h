@@ -852,6 +852,39 @@ int64_t crb_winograd4_wgrad_workspace_bytes(int cin, int cout);
 int crb_winograd4_wgrad(const float* x, const float* dy, float* dw, int64_t so, int64_t si, int64_t sky, int64_t skx,
                         int N, int H, int W, int cin, int cout, void* workspace, int64_t workspace_bytes, void* stream);
 
+/* Transposed convolutions with kernel = stride as row GEMMs on the bf16 matrix pipe (csrc/rows_gemm4.hip): a channels_last map is
+ * the row matrix (pixels x channels), so ConvTranspose2d(cin -> cout, k = s, stride = s, no padding, no bias, groups 1) is
+ * X[N H W x cin] . W[cin x s s cout] with the s * s result blocks of a row scattered to the output pixels (s h + a, s w + b); the input
+ * gradient gathers those pixels and contracts over (tap, cout); the weight gradient contracts over the rows. f32 in, f32 out:
+ * operands are written as exact sums of three bf16 values (the split of crb_conv3x3_winograd4_nhwc) and every product runs as six
+ * bf16 MFMA passes with f32 accumulation. No atomics: all three are bit-reproducible. An Inf operand turns the entries it reaches
+ * into NaN (inf - inf in the split), values below 2^-110 lose their low pieces to flushing.
+ * replaces: torch.nn.ConvTranspose2d(C, U, s, stride=s, bias=False) of the up-sampling branches of
+ *           pcdet/models/backbones_2d/base_bev_backbone.py:52-58 (MIOpen / CK backward-data forward, MIOpen igemm input and weight
+ *           gradients, hipBLASLt f32 GEMMs for s = 1).
+ * w: the ConvTranspose2d weight (cin, cout, s, s) given by its element strides (s_ci, s_co, s_a, s_b) (a Conv2d 1x1 weight: swap the
+ * first two). direction: 0 = forward, 1 = input gradient, 2 = weight gradient. stride in {1, 2}.
+ * crb_rows_gemm4_supported: forward cin % 32 == 0 and cout % 128 == 0; input gradient cout % 32 == 0 and cin % 128 == 0; weight
+ *   gradient cin % 256 == 0 and cout % 256 == 0; channel counts <= 4096.
+ * crb_rows_gemm4_weights: image (crb_rows_gemm4_weights_bytes) of direction 0 or 1: [n / 32][k / 16][piece 3][lane 64][8 bf16] of
+ *   Wm[k][n], forward k = ci, n = t cout + co; input gradient k = t cout + co, n = ci (t = a s + b); lane (r, h), element j of k step
+ *   2 c + u holds k = 32 c + 16 h + 8 u + j, n = 32 (n / 32) + r.
+ * crb_rows_gemm4_forward: x (N,H,W,cin) NHWC, image of direction 0 -> y (N,sH,sW,cout) NHWC.
+ * crb_rows_gemm4_input_grad: dy (N,sH,sW,cout), image of direction 1 -> dx (N,H,W,cin).
+ * crb_rows_gemm4_wgrad: x, dy as above -> dw written with the weight's element strides; partial sums per range of rows in the
+ *   workspace (crb_rows_gemm4_wgrad_workspace_bytes), added in range order in double. */
+int crb_rows_gemm4_supported(int cin, int cout, int stride, int direction);
+int64_t crb_rows_gemm4_weights_bytes(int cin, int cout, int stride);
+int crb_rows_gemm4_weights(const float* w, int64_t s_ci, int64_t s_co, int64_t s_a, int64_t s_b, void* image, int cin, int cout,
+                           int stride, int direction, void* stream);
+int crb_rows_gemm4_forward(const float* x, const void* image, float* y, int N, int H, int W, int cin, int cout, int stride,
+                           void* stream);
+int crb_rows_gemm4_input_grad(const float* dy, const void* image, float* dx, int N, int H, int W, int cin, int cout, int stride,
+                              void* stream);
+int64_t crb_rows_gemm4_wgrad_workspace_bytes(int cin, int cout, int stride);
+int crb_rows_gemm4_wgrad(const float* x, const float* dy, float* dw, int64_t s_ci, int64_t s_co, int64_t s_a, int64_t s_b, int N,
+                         int H, int W, int cin, int cout, int stride, void* workspace, int64_t workspace_bytes, void* stream);
+
 /* Scheduling hint, no reference counterpart: PV-RCNN's keypoint sampling (crb_furthest_point_sampling_stack on a side stream under
  * the backbones) holds one CU per frame for ~5 ms while the persistent one-workgroup-per-CU Winograd launches of the BEV backbone
  * run on the main stream. crb_cu_reservation(cus, stream) right before such a kernel, crb_cu_reservation(0, stream) right after it

@@ -1,4 +1,4 @@
-"""Build check of csrc/winograd_conv4.hip and csrc/winograd_wgrad4.hip: the kernels name their accumulator AGPRs in inline asm, so the
+"""Build check of csrc/winograd_conv4.hip, csrc/winograd_wgrad4.hip and csrc/rows_gemm4.hip: the kernels name their accumulator AGPRs in inline asm, so the
 compiler must not put anything of its own there. Compiles each file to ISA and fails if a compiler-generated v_accvgpr_write (VGPR
 source) targets an accumulator register, or if a kernel uses scratch. The weight-gradient kernel also requests its pixels in inline
 asm (global_load_dword, waited for by hand): between such a load and the counter wait that covers it nothing else may read or write
@@ -12,7 +12,8 @@ import tempfile
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, 'crb-active-3ddet_amd', 'csrc')
-SOURCES = (('winograd_conv4.hip', r'winograd4([bc]?)_kernel'), ('winograd_wgrad4.hip', r'winograd4_wgrad()_kernel'))
+SOURCES = (('winograd_conv4.hip', r'winograd4([bc]?)_kernel'), ('winograd_wgrad4.hip', r'winograd4_wgrad()_kernel'),
+           ('rows_gemm4.hip', r'rows_gemm4()_(?:wgrad_)?kernel'))
 
 
 def _regs(line):
@@ -77,7 +78,7 @@ def main(measure=False):
     if bad:
         print('\n'.join(bad[:20]))
         raise SystemExit('the compiler touched registers the kernels manage by hand (%d findings)' % len(bad))
-    print('winograd_conv4.hip / winograd_wgrad4.hip ISA check ok (%s)' % ('measure' if measure else 'product'))
+    print('winograd_conv4.hip / winograd_wgrad4.hip / rows_gemm4.hip ISA check ok (%s)' % ('measure' if measure else 'product'))
 
 
 if __name__ == '__main__':
