@@ -3,7 +3,8 @@ collate layout of DatasetTemplate.collate_batch (pcdet/datasets/dataset.py:160-2
 pcdet/datasets/__init__.py:26-46 and the two loader builders the reference's tools/train.py and active loop call
 (build_dataloader :49-78, build_active_dataloader :80-181) with the reference's signatures and return tuples.
 
-Real-dataset readers / augmentors are out of scope: the registry below answers 'KittiDataset' and
+Real-dataset readers are out of scope (of the augmentors the four world steps are provided, see
+pcdet/datasets/augmentor): the registry below answers 'KittiDataset' and
 'WaymoDataset' with synthetic clouds of that shape — ONLY when the config asks for it (dataset_cfg.SYNTHETIC present, or
 CRB_SYNTHETIC_DATA=1 in the environment). A reference config that names a real dataset (DATA_PATH / INFO_PATH / root_path)
 without that opt-in is refused loudly instead of training and selecting on fake frames."""
@@ -44,6 +45,8 @@ class _ConfiguredSynthetic(SyntheticDataset):
                          kind=self.KIND, training=training, first_frame=int(syn.get('FIRST_FRAME', 0)),
                          device_voxelize=bool(syn.get('DEVICE_VOXELIZE', True)), class_names=class_names)
         self.dataset_cfg, self.root_path, self.logger = dataset_cfg, root_path, logger
+        if training and dataset_cfg is not None and dataset_cfg.get('DATA_AUGMENTOR', None) is not None:
+            self.set_data_augmentor(dataset_cfg.DATA_AUGMENTOR, root_path=root_path, logger=logger)
 
     def __getstate__(self):
         d = dict(self.__dict__)

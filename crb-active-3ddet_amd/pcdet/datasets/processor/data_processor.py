@@ -129,11 +129,18 @@ class DeviceDataProcessor(object):
             self.grid_size = np.round(g).astype(np.int64)
             self.voxel_size = self.voxel_cfg.VOXEL_SIZE
 
-    def process_batch(self, points_list, gt_boxes_list=None, frame_ids=None):
+    def process_batch(self, points_list, gt_boxes_list=None, frame_ids=None, augmentor=None):
         """points_list: per-frame (n_i, C) float32 numpy arrays -> batch dict with device 'points' (N,1+C),
-        'point_frame_offsets' (B+1) int32, host-padded 'gt_boxes' (B,G,8) on the device"""
+        'point_frame_offsets' (B+1) int32, host-padded 'gt_boxes' (B,G,8) on the device.
+        augmentor: a DeviceDataAugmentor (pcdet.datasets.augmentor), or None for un-augmented frames. On a CUDA device the frames
+        are transformed, range-masked and concatenated by crb_augment_mask_points and the boxes by crb_augment_boxes; on
+        device='cpu' every frame goes through the host DataAugmentor first (same draws, same arithmetic)."""
         torch = self.torch
         from ...utils import box_utils, common_utils
+        if augmentor is not None:
+            if self.device.type == 'cuda':
+                return self._process_batch_augmented(points_list, gt_boxes_list, frame_ids, augmentor)
+            points_list, gt_boxes_list = self._host_augment(points_list, gt_boxes_list, augmentor)
         B = len(points_list)
         counts = [len(p) for p in points_list]
         host = torch.from_numpy(np.concatenate(points_list, 0).astype(np.float32, copy=False))
@@ -168,6 +175,68 @@ class DeviceDataProcessor(object):
             for k, g in enumerate(gts):
                 pad[k, :len(g)] = g
             batch['gt_boxes'] = torch.from_numpy(pad).to(self.device, non_blocking=True)
+        if frame_ids is not None:
+            batch['frame_id'] = np.array(frame_ids)
+        return batch
+
+    @staticmethod
+    def _host_augment(points_list, gt_boxes_list, augmentor):
+        """the host route: DataAugmentor.forward on copies of the frames, one by one and in order. The boxes of a batch carry their
+        class in the last column, which the augmentor never sees (the reference appends it after augmentation)"""
+        pts_out, gt_out = [], []
+        for k, p in enumerate(points_list):
+            g = np.asarray(gt_boxes_list[k], dtype=np.float32) if gt_boxes_list is not None else None
+            if g is None or g.ndim != 2 or g.shape[1] == 0:
+                g = np.zeros((0, 8), dtype=np.float32)
+            d = augmentor.host.forward({'points': np.array(p, dtype=np.float32), 'gt_boxes': g[:, :-1].copy()})
+            pts_out.append(d['points'])
+            gt_out.append(np.concatenate([d['gt_boxes'], g[:, -1:]], axis=1))
+        return pts_out, (gt_out if gt_boxes_list is not None else None)
+
+    def _process_batch_augmented(self, points_list, gt_boxes_list, frame_ids, augmentor):
+        """the device route: one upload of the raw frames, of the drawn parameters and of the padded boxes; transform + range mask +
+        frame concatenation in crb_augment_mask_points (three launches), the boxes in crb_augment_boxes (one); one read-back of
+        the kept totals. Replaces the comparison / boolean-index / repeat_interleave launches of the un-augmented path."""
+        torch = self.torch
+        from crbhip import augment
+        dev = self.device
+        B = len(points_list)
+        params_h, angles_h = augmentor.draw_batch(B)
+        counts = [len(p) for p in points_list]
+        host = torch.from_numpy(np.concatenate(points_list, 0).astype(np.float32, copy=False))
+        pts = host.pin_memory().to(dev, non_blocking=True)
+        have_boxes = gt_boxes_list is not None
+        if have_boxes:
+            gts = [np.asarray(g, dtype=np.float32) for g in gt_boxes_list]
+            width = gts[0].shape[-1] if len(gts[0].shape) == 2 and gts[0].shape[-1] else 8
+            G = max(1, max(len(g) for g in gts))
+            pad = np.zeros((B, G, width), dtype=np.float32)
+            for k, g in enumerate(gts):
+                pad[k, :len(g)] = g
+        # the small operands travel as one f32 and one i32 buffer: [params (B,8) | angles (B) | boxes (B,G,W)], [offsets (B+1) | box counts (B)]
+        f_host = np.concatenate([params_h.ravel(), angles_h] + ([pad.ravel()] if have_boxes else []))
+        i_host = np.concatenate([[0], np.cumsum(counts), [len(g) for g in gts] if have_boxes else []]).astype(np.int32)
+        f_dev = torch.from_numpy(f_host).pin_memory().to(dev, non_blocking=True)
+        i_dev = torch.from_numpy(i_host).pin_memory().to(dev, non_blocking=True)
+        params, angles = f_dev[:8 * B].view(B, 8), f_dev[8 * B:9 * B]
+        r = [float(v) for v in self.point_cloud_range]
+        out, new_off = augment.augment_mask_points(pts, i_dev[:B + 1], params, r, mask=self.mask_cfg is not None, xyz_col=0,
+                                                   frame_col=True, lazy=True)
+        sizes = new_off
+        if have_boxes:
+            mask_boxes = bool(self.mask_cfg is not None and self.mask_cfg.REMOVE_OUTSIDE_BOXES and self.training)
+            boxes, new_counts = augment.augment_boxes(
+                f_dev[9 * B:].view(B, G, width), i_dev[B + 1:], params, angles, r, mask=mask_boxes,
+                min_num_corners=self.mask_cfg.get('min_num_corners', 1) if mask_boxes else 1)
+            sizes = torch.cat([new_off, new_counts])
+        sizes_h = sizes.cpu().tolist()                          # the one device->host size read-back of the batch
+        out = out[:sizes_h[B]]
+        if self.shuffle:
+            key = out[:, 0].double() + torch.rand(out.shape[0], device=dev, generator=self.generator, dtype=torch.float64)
+            out = out[torch.argsort(key)]
+        batch = {'points': out, 'point_frame_offsets': new_off, 'batch_size': B}
+        if have_boxes:
+            batch['gt_boxes'] = boxes[:, :max(1, max(sizes_h[B + 1:]))].contiguous()
         if frame_ids is not None:
             batch['frame_id'] = np.array(frame_ids)
         return batch

@@ -50,6 +50,18 @@ class SyntheticDataset(Dataset):
         self.frame_ids = self.sample_id_list
         self.infos = self.kitti_infos
         self._voxel_generator = None
+        self.data_augmentor = self._range_mask = None
+
+    def set_data_augmentor(self, augmentor_configs, root_path=None, logger=None):
+        """dataset_cfg.DATA_AUGMENTOR: in training mode __getitem__ runs the host DataAugmentor and then the host DataProcessor
+        range masks on points and boxes (DatasetTemplate.prepare_data, pcdet/datasets/dataset.py:106-158)"""
+        from ..config import EasyDict
+        from .augmentor import DataAugmentor
+        from .processor.data_processor import DataProcessor
+        self.data_augmentor = DataAugmentor(root_path, augmentor_configs, self.class_names, logger=logger)
+        self._range_mask = DataProcessor(
+            [EasyDict({'NAME': 'mask_points_and_boxes_outside_range', 'REMOVE_OUTSIDE_BOXES': True})], self.point_cloud_range,
+            training=True, num_point_features=self.point_feature_encoder.num_point_features)
 
     def sync_id_views(self, waymo=False):
         """the active loop re-assigns (sample_id_list, kitti_infos) for KITTI or (frame_ids, infos) for Waymo
@@ -69,6 +81,12 @@ class SyntheticDataset(Dataset):
     def __getitem__(self, index):
         fid = self.sample_id_list[index]
         pts, boxes = syn.kitti_frame(int(fid), self.n_points, waymo=(self.kind == 'waymo'))
+        if self.data_augmentor is not None and self.training:
+            # the augmentor sees the box coordinates only; the class column joins again behind it (as in the reference)
+            a = self.data_augmentor.forward({'points': pts, 'gt_boxes': boxes[:, :-1].copy()})
+            a['gt_boxes'] = np.concatenate([a['gt_boxes'], boxes[:, -1:]], axis=1)
+            a = self._range_mask.forward(a)
+            pts, boxes = a['points'], a['gt_boxes']
         d = {'points': pts, 'gt_boxes': boxes, 'frame_id': fid, 'use_lead_xyz': True}
         if not self.device_voxelize:
             from .processor.data_processor import VoxelGeneratorWrapper

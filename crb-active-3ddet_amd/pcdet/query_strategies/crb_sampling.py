@@ -327,8 +327,9 @@ class CRBSampling(Strategy):
         (crb_sampling.py:174-212). -> (len(frame_indices), 65536) device tensor"""
         # NOTE (deliberate departure): the reference builds the stage-2 loader with training=True, i.e. the frames go
         # through the train-mode data pipeline (augmentation, point shuffling) before the bs=1 pass (crb_sampling.py:152-161).
-        # Augmentors are out of scope (SURVEY §2.1 row 15); here stage-2 frames come from the same pool dataset object
-        # as stage 1, un-augmented, while the MODEL runs in train mode exactly as in the reference.
+        # The world augmentors exist now (pcdet/datasets/augmentor; on the device DeviceDataProcessor.process_batch(...,
+        # augmentor=DeviceDataAugmentor)), but stage 2 is not wired to them yet (DESIGN §7): its frames still come from the same
+        # pool dataset object as stage 1, un-augmented, while the MODEL runs in train mode exactly as in the reference.
         model = self.detector
         rec = scoring.unpack_records(records, self.layout)
         model.train()

@@ -52,6 +52,45 @@ int crb_voxelize(const float* points, int64_t n_points, int num_features,
                  void* workspace, int64_t workspace_bytes, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * a0  World augmentation (+ range mask + frame concat) for a batch of training frames
+ * replaces: pcdet/datasets/augmentor/augmentor_utils.py:8-81 (random_flip_along_x / _y, global_rotation, global_scaling) and
+ *           :124-175 (random_translation_along_x / _y / _z) as queued by pcdet/datasets/augmentor/data_augmentor.py:43-117 and
+ *           finished by :229-258 (limit_period of the heading), then pcdet/datasets/processor/data_processor.py:78-91
+ *           (mask_points_and_boxes_outside_range) with pcdet/utils/common_utils.py:60-63 (mask_points_by_range) and
+ *           pcdet/utils/box_utils.py:56-72 (mask_boxes_outside_range_numpy, corners of :28-53), and the frame-index column of
+ *           pcdet/datasets/dataset.py:160-229 (collate_batch).
+ *
+ * params (B, 8) f32 device, 16-byte aligned, one row per frame: [flip_x, flip_y, c, s, scale, tx, ty, tz]. flip_* != 0 flips;
+ *   c = f32(cos a), s = f32(sin a) of the drawn angle a. The random draws are the caller's (host, np.random). Steps run in the fixed
+ *   order flip x (y = -y), flip y (x = -x), rotation (x' = x c - y s, y' = x s + y c), scaling (xyz *= scale), translation; f32,
+ *   one rounding per operation. A step at its identity value (flip 0, (c, s) = (1, 0), scale 1, offset 0) is skipped, so identity
+ *   parameters reproduce every bit of the input. range6: HOST array [x0, y0, z0, x1, y1, z1].
+ *
+ * crb_augment_mask_points: points = n_points rows, row_stride floats apart, xyz at column xyz_col followed by num_features - 3
+ *   feature columns that pass through (xyz_col = 0: raw (N, C) rows; 1: the batch layout (N, 1 + C)); frame_offsets (B+1) i32
+ *   device. Each transformed point is kept if !do_mask or x0 <= x <= x1 and y0 <= y <= y1 (x and y only, bounds inclusive).
+ *   Kept rows go to out_points in their original order, frame after frame, as dense rows of out_frame_col + num_features floats
+ *   (out_frame_col = 1: column 0 = frame index as f32); out_points holds n_points rows, rows past the total stay untouched.
+ *   new_frame_offsets (B+1) i32 device: offsets of the kept rows, [B] = total. Three launches, no atomics: same bits every call.
+ * crb_augment_boxes: gt_boxes (B, G, W) f32, W = 8 or 10: W - 1 box coordinates [x, y, z, dx, dy, dz, heading, (vx, vy)] + class;
+ *   counts (B) i32: valid rows per frame, the rest is padding. Centre, size, heading and velocity get the same transforms
+ *   (flip x: heading = -heading, vy = -vy; flip y: heading = -(heading + f32(pi)), vx = -vx; rotation: heading += rot_angles[b],
+ *   the f32 of the drawn angle, (vx, vy) rotated; scaling: columns 0..5), then heading = h - floor(h / f32(2 pi) + 0.5) * f32(2 pi),
+ *   then, if do_mask, boxes with fewer than min_num_corners corners inside range6 on all three axes are removed (corners:
+ *   size * (+-0.5) rotated by c = f32(cos((double)heading)), s = f32(sin((double)heading)), plus the centre). Kept rows are compacted
+ *   in order inside each frame of out_boxes (B, G, W) (must not alias gt_boxes), all other rows are zero; new_counts (B) i32.
+ *   rot_angles (B) f32 device or NULL (= 0). One launch.
+ * ---------------------------------------------------------------------------------------------- */
+int64_t crb_augment_mask_points_workspace_bytes(int64_t n_points, int B);
+int crb_augment_mask_points(const float* points, int64_t n_points, int64_t row_stride, int xyz_col, int num_features,
+                            const int32_t* frame_offsets, int B, const float* params, const float* range6, int do_mask,
+                            float* out_points, int out_frame_col, int32_t* new_frame_offsets,
+                            void* workspace, int64_t workspace_bytes, void* stream);
+int crb_augment_boxes(const float* gt_boxes, const int32_t* counts, int B, int G, int W, const float* params,
+                      const float* rot_angles, const float* range6, int do_mask, int min_num_corners,
+                      float* out_boxes, int32_t* new_counts, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * a4  Sparse 3D convolution: rulebooks + gather-GEMM fwd / dgrad / wgrad
  * replaces: spconv.pytorch.SubMConv3d / SparseConv3d / SparseConvTensor (third-party spconv-cu113 v2.1.21,
  *           not vendored) as used by pcdet/models/backbones_3d/spconv_backbone.py:8-27,77-117,141-157 and
