@@ -3,7 +3,7 @@ collate layout of DatasetTemplate.collate_batch (pcdet/datasets/dataset.py:160-2
 pcdet/datasets/__init__.py:26-46 and the two loader builders the reference's tools/train.py and active loop call
 (build_dataloader :49-78, build_active_dataloader :80-181) with the reference's signatures and return tuples.
 
-Real-dataset readers are out of scope (of the augmentors the four world steps are provided, see
+Real-dataset readers are out of scope (of the augmentors gt_sampling and the four world steps are provided, see
 pcdet/datasets/augmentor): the registry below answers 'KittiDataset' and
 'WaymoDataset' with synthetic clouds of that shape — ONLY when the config asks for it (dataset_cfg.SYNTHETIC present, or
 CRB_SYNTHETIC_DATA=1 in the environment). A reference config that names a real dataset (DATA_PATH / INFO_PATH / root_path)

@@ -182,30 +182,40 @@ class DeviceDataProcessor(object):
     @staticmethod
     def _host_augment(points_list, gt_boxes_list, augmentor):
         """the host route: DataAugmentor.forward on copies of the frames, one by one and in order. The boxes of a batch carry their
-        class in the last column, which the augmentor never sees (the reference appends it after augmentation)"""
+        class in the last column, which the augmentor never sees (the reference appends it after augmentation); a gt_sampling step
+        gets the names that column stands for and the augmentor's labelled set, and the column is rebuilt from the names behind it"""
         pts_out, gt_out = [], []
+        names = np.array(augmentor.class_names) if augmentor.sampler is not None else None
         for k, p in enumerate(points_list):
             g = np.asarray(gt_boxes_list[k], dtype=np.float32) if gt_boxes_list is not None else None
             if g is None or g.ndim != 2 or g.shape[1] == 0:
                 g = np.zeros((0, 8), dtype=np.float32)
-            d = augmentor.host.forward({'points': np.array(p, dtype=np.float32), 'gt_boxes': g[:, :-1].copy()})
+            d = {'points': np.array(p, dtype=np.float32), 'gt_boxes': g[:, :-1].copy()}
+            if names is not None:
+                d['gt_names'] = names[g[:, -1].astype(np.int64) - 1] if len(g) else np.zeros((0,), dtype=names.dtype)
+                d['sample_id_list'] = augmentor.labelled
+            d = augmentor.host.forward(d)
+            cls = g[:, -1:]
+            if names is not None:
+                cls = np.array([[augmentor.class_names.index(n) + 1] for n in d['gt_names']], dtype=np.float32).reshape(-1, 1)
             pts_out.append(d['points'])
-            gt_out.append(np.concatenate([d['gt_boxes'], g[:, -1:]], axis=1))
+            gt_out.append(np.concatenate([d['gt_boxes'], cls], axis=1))
         return pts_out, (gt_out if gt_boxes_list is not None else None)
 
     def _process_batch_augmented(self, points_list, gt_boxes_list, frame_ids, augmentor):
         """the device route: one upload of the raw frames, of the drawn parameters and of the padded boxes; transform + range mask +
         frame concatenation in crb_augment_mask_points (three launches), the boxes in crb_augment_boxes (one); one read-back of
-        the kept totals. Replaces the comparison / boolean-index / repeat_interleave launches of the un-augmented path."""
+        the kept totals. Replaces the comparison / boolean-index / repeat_interleave launches of the un-augmented path.
+        With a gt_sampling step the drawn candidates travel in the same two uploads; crb_gt_sample_select and crb_gt_sample_paste
+        run in front (collision test, point removal and paste against the device-resident object database), their outputs feed
+        the two kernels above, and the read-back stays the only one. The batch then also carries 'gt_sampling_valid' (B, S) u8 on
+        the device and 'gt_sampling_groups', the per-frame [(class, [database indices])] that were drawn."""
         torch = self.torch
         from crbhip import augment
         dev = self.device
         B = len(points_list)
-        params_h, angles_h = augmentor.draw_batch(B)
-        counts = [len(p) for p in points_list]
-        host = torch.from_numpy(np.concatenate(points_list, 0).astype(np.float32, copy=False))
-        pts = host.pin_memory().to(dev, non_blocking=True)
         have_boxes = gt_boxes_list is not None
+        sampling = getattr(augmentor, 'sampler', None) is not None
         if have_boxes:
             gts = [np.asarray(g, dtype=np.float32) for g in gt_boxes_list]
             width = gts[0].shape[-1] if len(gts[0].shape) == 2 and gts[0].shape[-1] else 8
@@ -213,20 +223,61 @@ class DeviceDataProcessor(object):
             pad = np.zeros((B, G, width), dtype=np.float32)
             for k, g in enumerate(gts):
                 pad[k, :len(g)] = g
-        # the small operands travel as one f32 and one i32 buffer: [params (B,8) | angles (B) | boxes (B,G,W)], [offsets (B+1) | box counts (B)]
-        f_host = np.concatenate([params_h.ravel(), angles_h] + ([pad.ravel()] if have_boxes else []))
-        i_host = np.concatenate([[0], np.cumsum(counts), [len(g) for g in gts] if have_boxes else []]).astype(np.int32)
+        draw = None
+        if sampling:
+            if not have_boxes or width != 8:
+                raise ValueError('gt_sampling needs the frames\' boxes as (G, 8) rows [7 coordinates, class]')
+            names = np.array(augmentor.class_names)
+            params_h, angles_h, draw = augmentor.draw_batch(
+                B, gt_names=[names[g[:, -1].astype(np.int64) - 1] if len(g) else np.zeros((0,), dtype=names.dtype) for g in gts])
+            # one more identity row: the frame that stands for the unused tail of the paste buffer (see below)
+            params_h = np.concatenate([params_h, augmentor.identity(1)[0]], 0)
+        else:
+            params_h, angles_h = augmentor.draw_batch(B)
+        P = len(params_h)
+        counts = [len(p) for p in points_list]
+        host = torch.from_numpy(np.concatenate(points_list, 0).astype(np.float32, copy=False))
+        pts = host.pin_memory().to(dev, non_blocking=True)
+        # the small operands travel as one f32 and one i32 buffer:
+        # [params (P,8) | angles (B) | boxes (B,G,W) | candidates (B,S,20)], [offsets (B+1) | box counts (B) | objects (B,S) | groups (B,K+1)]
+        f_parts = [params_h.ravel(), angles_h] + ([pad.ravel()] if have_boxes else [])
+        i_parts = [[0], np.cumsum(counts), [len(g) for g in gts] if have_boxes else []]
+        if sampling:
+            f_parts.append(draw['cand'].ravel())
+            i_parts += [draw['cand_obj'].ravel(), draw['group_offsets'].ravel()]
+        f_host = np.concatenate(f_parts)
+        i_host = np.concatenate(i_parts).astype(np.int32)
         f_dev = torch.from_numpy(f_host).pin_memory().to(dev, non_blocking=True)
         i_dev = torch.from_numpy(i_host).pin_memory().to(dev, non_blocking=True)
-        params, angles = f_dev[:8 * B].view(B, 8), f_dev[8 * B:9 * B]
+        params, angles = f_dev[:8 * P].view(P, 8), f_dev[8 * P:8 * P + B]
+        f_at = 8 * P + B
+        off, box_counts = i_dev[:B + 1], i_dev[B + 1:2 * B + 1]
+        if have_boxes:
+            boxes_in = f_dev[f_at:f_at + B * G * width].view(B, G, width)
+            f_at += B * G * width
+        valid = None
+        if sampling:
+            from crbhip import gt_sampling
+            S, K1 = draw['cand'].shape[1], draw['group_offsets'].shape[1]
+            cand = f_dev[f_at:f_at + B * S * 20].view(B, S, 20)
+            cand_obj = i_dev[2 * B + 1:2 * B + 1 + B * S].view(B, S)
+            group_off = i_dev[2 * B + 1 + B * S:].view(B, K1)
+            db = augmentor.database.device_tensors(dev)
+            valid, boxes_in, box_counts, cand_rows, paste_counts = gt_sampling.select(boxes_in, box_counts, cand, cand_obj,
+                                                                                      group_off, db)
+            # the paste buffer holds the scene points plus the points of ALL candidates (known here, no read-back); its offsets
+            # end with [total, capacity], so that to crb_augment_mask_points the untouched tail is frame B, behind the real ones
+            pts, off = gt_sampling.paste(pts, off, cand, cand_obj, valid, cand_rows, paste_counts, db,
+                                         capacity=len(host) + draw['n_cand_points'], lazy=True)
         r = [float(v) for v in self.point_cloud_range]
-        out, new_off = augment.augment_mask_points(pts, i_dev[:B + 1], params, r, mask=self.mask_cfg is not None, xyz_col=0,
+        out, new_off = augment.augment_mask_points(pts, off, params, r, mask=self.mask_cfg is not None, xyz_col=0,
                                                    frame_col=True, lazy=True)
+        new_off = new_off[:B + 1]
         sizes = new_off
         if have_boxes:
             mask_boxes = bool(self.mask_cfg is not None and self.mask_cfg.REMOVE_OUTSIDE_BOXES and self.training)
             boxes, new_counts = augment.augment_boxes(
-                f_dev[9 * B:].view(B, G, width), i_dev[B + 1:], params, angles, r, mask=mask_boxes,
+                boxes_in, box_counts, params[:B], angles, r, mask=mask_boxes,
                 min_num_corners=self.mask_cfg.get('min_num_corners', 1) if mask_boxes else 1)
             sizes = torch.cat([new_off, new_counts])
         sizes_h = sizes.cpu().tolist()                          # the one device->host size read-back of the batch
@@ -237,6 +288,9 @@ class DeviceDataProcessor(object):
         batch = {'points': out, 'point_frame_offsets': new_off, 'batch_size': B}
         if have_boxes:
             batch['gt_boxes'] = boxes[:, :max(1, max(sizes_h[B + 1:]))].contiguous()
+        if sampling:
+            batch['gt_sampling_valid'] = valid
+            batch['gt_sampling_groups'] = draw['groups']
         if frame_ids is not None:
             batch['frame_id'] = np.array(frame_ids)
         return batch

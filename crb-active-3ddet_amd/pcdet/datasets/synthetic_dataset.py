@@ -51,17 +51,74 @@ class SyntheticDataset(Dataset):
         self.infos = self.kitti_infos
         self._voxel_generator = None
         self.data_augmentor = self._range_mask = None
+        self.active_sampling = True
 
-    def set_data_augmentor(self, augmentor_configs, root_path=None, logger=None):
+    def set_data_augmentor(self, augmentor_configs, root_path=None, logger=None, active=True, **sampler_args):
         """dataset_cfg.DATA_AUGMENTOR: in training mode __getitem__ runs the host DataAugmentor and then the host DataProcessor
-        range masks on points and boxes (DatasetTemplate.prepare_data, pcdet/datasets/dataset.py:106-158)"""
+        range masks on points and boxes (DatasetTemplate.prepare_data, pcdet/datasets/dataset.py:106-158).
+        root_path: where a gt_sampling step finds its DB_INFO_PATH pickles and gt_database files; sampler_args (bev_iou=, db_infos=)
+        go to its DataBaseSampler. active: the sampler only pastes objects cut from the frames of sample_id_list (the reference's
+        cfg.ACTIVE_TRAIN branch); False selects the non-active branch."""
         from ..config import EasyDict
         from .augmentor import DataAugmentor
         from .processor.data_processor import DataProcessor
-        self.data_augmentor = DataAugmentor(root_path, augmentor_configs, self.class_names, logger=logger)
+        self.data_augmentor = DataAugmentor(root_path, augmentor_configs, self.class_names, logger=logger, **sampler_args)
+        self.active_sampling = bool(active)
         self._range_mask = DataProcessor(
             [EasyDict({'NAME': 'mask_points_and_boxes_outside_range', 'REMOVE_OUTSIDE_BOXES': True})], self.point_cloud_range,
             training=True, num_point_features=self.point_feature_encoder.num_point_features)
+
+    WAYMO_SEQUENCE = 'segment-synthetic'
+
+    def database_sample_id(self, fid):
+        """the id under which the object database files a frame: KITTI the frame id itself (image_idx), Waymo
+        sequence_name + '_' + three-digit sample_idx (what the reference's Waymo branch of the sampler assembles)"""
+        return fid if self.kind == 'kitti' else '%s_%03d' % (self.WAYMO_SEQUENCE, int(fid))
+
+    def labelled_sample_ids(self):
+        """sample_id_list in the form above, as a set (rebuilt when the active loop re-assigns the list)"""
+        key = (id(self.sample_id_list), len(self.sample_id_list))
+        if getattr(self, '_labelled_ids', (None, None))[0] != key:
+            self._labelled_ids = (key, frozenset(self.database_sample_id(f) for f in self.sample_id_list))
+        return self._labelled_ids[1]
+
+    def create_groundtruth_database(self, save_path=None, used_classes=None):
+        """the ground-truth database of this dataset's frames in the reference's format (kitti_dataset.py:224-274): per object of
+        every frame the (un-augmented) points inside its box, xyz relative to the box centre, membership by the CPU twin's rule
+        (database_sampler.points_in_removal_boxes, no extra width).
+        save_path: writes gt_database/<frame>_<Name>_<i>.bin (f32 rows of num_point_features columns) and dbinfos_train.pkl
+        = {class name: [{'name', 'path', 'image_idx', 'gt_idx', 'box3d_lidar', 'num_points_in_gt', 'difficulty': 0, 'bbox',
+        'score'}]} (+ 'sequence_name', 'sample_idx' for the Waymo kind) under it. None: nothing is written and the infos carry the
+        arrays under 'points' with 'path' None. -> the infos"""
+        import pickle
+        from pathlib import Path
+        from .augmentor import database_sampler as dbs
+        if save_path is not None:
+            (Path(save_path) / 'gt_database').mkdir(parents=True, exist_ok=True)
+        all_db_infos = {}
+        for fid in self.sample_id_list:
+            points, boxes = syn.kitti_frame(int(fid), self.n_points, waymo=(self.kind == 'waymo'))
+            inside = dbs.points_in_removal_boxes(points[:, 0:3], dbs.removal_boxes(boxes[:, :7]))
+            for i in range(len(boxes)):
+                name = self.class_names[int(boxes[i, 7]) - 1]
+                gt_points = points[inside[i]].copy()
+                gt_points[:, :3] -= boxes[i, :3]
+                info = {'name': name, 'path': None, 'image_idx': fid, 'gt_idx': i, 'box3d_lidar': boxes[i, :7].copy(),
+                        'num_points_in_gt': gt_points.shape[0], 'difficulty': 0,
+                        'bbox': np.zeros((4,), dtype=np.float32), 'score': -1.0}
+                if self.kind == 'waymo':
+                    info.update({'sequence_name': self.WAYMO_SEQUENCE, 'sample_idx': int(fid)})
+                if save_path is not None:
+                    info['path'] = 'gt_database/%s_%s_%d.bin' % (fid, name, i)
+                    gt_points.tofile(str(Path(save_path) / info['path']))
+                else:
+                    info['points'] = gt_points
+                if used_classes is None or name in used_classes:
+                    all_db_infos.setdefault(name, []).append(info)
+        if save_path is not None:
+            with open(str(Path(save_path) / 'dbinfos_train.pkl'), 'wb') as f:
+                pickle.dump(all_db_infos, f)
+        return all_db_infos
 
     def sync_id_views(self, waymo=False):
         """the active loop re-assigns (sample_id_list, kitti_infos) for KITTI or (frame_ids, infos) for Waymo
@@ -83,8 +140,13 @@ class SyntheticDataset(Dataset):
         pts, boxes = syn.kitti_frame(int(fid), self.n_points, waymo=(self.kind == 'waymo'))
         if self.data_augmentor is not None and self.training:
             # the augmentor sees the box coordinates only; the class column joins again behind it (as in the reference)
-            a = self.data_augmentor.forward({'points': pts, 'gt_boxes': boxes[:, :-1].copy()})
-            a['gt_boxes'] = np.concatenate([a['gt_boxes'], boxes[:, -1:]], axis=1)
+            names = np.array(self.class_names)
+            a = self.data_augmentor.forward({
+                'points': pts, 'gt_boxes': boxes[:, :-1].copy(), 'gt_names': names[boxes[:, -1].astype(np.int64) - 1],
+                'sample_id_list': self.labelled_sample_ids() if self.active_sampling else None})
+            # (gt_sampling appends boxes: the class column follows the names)
+            cls = np.array([self.class_names.index(n) + 1 for n in a['gt_names']], dtype=np.float32).reshape(-1, 1)
+            a['gt_boxes'] = np.concatenate([a['gt_boxes'], cls], axis=1)
             a = self._range_mask.forward(a)
             pts, boxes = a['points'], a['gt_boxes']
         d = {'points': pts, 'gt_boxes': boxes, 'frame_id': fid, 'use_lead_xyz': True}

@@ -157,3 +157,21 @@ def pv_rcnn_llal_cfg():
     c.ACTIVE_TRAIN.LOSS_NET_TRAIN_EPOCH = 10
     c.ACTIVE_TRAIN.pop('ACTIVE_CONFIG')
     return c
+
+
+def kitti_augmentor_cfg(db_info_path=None, use_road_plane=False, num_point_features=4):
+    """DATA_AUGMENTOR of tools/cfgs/dataset_configs/kitti_dataset.yaml:18-44 as a list of step configs: gt_sampling (Car:20,
+    Pedestrian:15, Cyclist:15, at least 5 points per object, LIMIT_WHOLE_SCENE), world flip about x, rotation, scaling.
+    db_info_path: the DB_INFO_PATH pickles under the augmentor's root_path (None: the database is handed over as db_infos=).
+    use_road_plane: the reference's True needs the road planes and the calibration of the real dataset, which synthetic frames do
+    not have; data_dict['road_plane'] / ['calib'] are read when it is set."""
+    return [
+        EasyDict({'NAME': 'gt_sampling', 'USE_ROAD_PLANE': bool(use_road_plane),
+                  'DB_INFO_PATH': list(db_info_path) if db_info_path else [],
+                  'PREPARE': {'filter_by_min_points': ['Car:5', 'Pedestrian:5', 'Cyclist:5'], 'filter_by_difficulty': [-1]},
+                  'SAMPLE_GROUPS': ['Car:20', 'Pedestrian:15', 'Cyclist:15'], 'NUM_POINT_FEATURES': int(num_point_features),
+                  'DATABASE_WITH_FAKELIDAR': False, 'REMOVE_EXTRA_WIDTH': [0.0, 0.0, 0.0], 'LIMIT_WHOLE_SCENE': True}),
+        EasyDict({'NAME': 'random_world_flip', 'ALONG_AXIS_LIST': ['x']}),
+        EasyDict({'NAME': 'random_world_rotation', 'WORLD_ROT_ANGLE': [-0.78539816, 0.78539816]}),
+        EasyDict({'NAME': 'random_world_scaling', 'WORLD_SCALE_RANGE': [0.95, 1.05]}),
+    ]

@@ -91,6 +91,57 @@ int crb_augment_boxes(const float* gt_boxes, const int32_t* counts, int B, int G
                       float* out_boxes, int32_t* new_counts, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * a0' gt_sampling for a batch of training frames: collision test of the drawn database objects, paste of the accepted ones
+ * replaces: pcdet/datasets/augmentor/database_sampler.py:150-234 (the IoU tests of DataBaseSampler.__call__ and
+ *           add_sampled_boxes_to_scene) with pcdet/ops/iou3d_nms/src/iou3d_cpu.cpp:232-252 (boxes_iou_bev_cpu),
+ *           pcdet/utils/box_utils.py:75-89,145-158 (remove_points_in_boxes3d, enlarge_box3d) and
+ *           pcdet/ops/roiaware_pool3d/src/roiaware_pool3d.cpp:121-167 (points_in_boxes_cpu, the CPU twin's rule).
+ *
+ * The candidate walk (sample_with_fixed_number, np.random) and the arithmetic on the candidate boxes are the caller's (host).
+ * cand (B, S, 20) f32 device, one record per candidate, a frame's candidates group after group in the order of SAMPLE_GROUPS:
+ *   [0..6]   x, y, z, dx, dy, dz, heading as they enter the collision test (after the fake-lidar conversion, before the road plane)
+ *   [7]      class as f32            [8] shift: road-plane z shift of the object, 0 when unused
+ *   [9..16]  removal box: cx, cy, cz (z - shift), dx, dy, dz (+ REMOVE_EXTRA_WIDTH), cosa = f32(cos(-(double)rz)),
+ *            sina = f32(sin(-(double)rz))
+ *   [17..19] offset added to the object's database points (xyz of the database box)
+ * cand_obj (B, S) i32 device: database object of each candidate; group_offsets (B, K + 1) i32 device: candidates [off[k], off[k+1])
+ *   of a frame form group k, off[K] = the frame's candidate count (<= S, the rest of the frame's S records is padding).
+ * Database: db_points (P, num_features) f32 with xyz relative to the box centre, obj_offsets (num_objects + 1) i32, both device.
+ *
+ * crb_gt_sample_select: gt_boxes (B, G, 8) f32 [x, y, z, dx, dy, dz, heading, class] with gt_counts (B) i32 valid rows. One
+ *   workgroup per frame walks the groups in order. Candidate s of group k is valid iff iou(s, o) == 0.0f for every box o existing
+ *   when group k is tested (the frame's own boxes and the valid candidates of earlier groups) and for every other candidate o of
+ *   group k; iou is the rotated BEV IoU of crb_boxes_pairwise(mode 1), the very same device function, candidate first. So two
+ *   candidates of one group that touch each other are both dropped, and a candidate whose only overlap is with a dropped candidate
+ *   of an earlier group is accepted.
+ *   valid (B, S) u8 (padding 0). out_boxes (B, G + S, 8): the frame's own rows, behind them the valid candidates in candidate order
+ *   as [x, y, z - shift, dx, dy, dz, heading, class] (one f32 subtraction), the rest zero; new_counts (B) i32.
+ *   cand_rows (B, S) i32: first row of a valid candidate's points inside its frame's pasted block (exclusive scan of the point counts
+ *   of the valid candidates in candidate order), -1 for the others; paste_counts (B) i32: pasted rows per frame.
+ *   Capacity: S <= 256 and G + S <= 512, else CRB_ERR_UNSUPPORTED. One launch.
+ * crb_gt_sample_paste: points (n_points, num_features) f32 dense rows, frame_offsets (B+1) i32. Output rows, frame after frame:
+ *   first the points of the frame's valid candidates in candidate order - database row with x + ox, y + oy, z + oz (separate f32
+ *   additions) and then z - shift (one more f32 subtraction, skipped when shift == 0), features copied - then the frame's own
+ *   points that lie in no valid candidate's removal box, in their original order, unchanged. A point is inside a removal box iff
+ *   !(fabsf(z - cz) > dz / 2) and, with sx = x - cx, sy = y - cy, lx = sx * cosa + sy * (-sina), ly = sx * sina + sy * cosa (every f32
+ *   product and sum rounded once, no FMA), (double)fabsf(lx) < (double)dx / 2 + (double)1e-2f and the same for ly / dy.
+ *   out_points holds `capacity` rows (>= n_points + the point counts of ALL candidates, which the host knows: no read-back); rows past
+ *   the total stay untouched. new_frame_offsets (B + 2) i32: offsets of the frames' rows, [B] = total, [B + 1] = capacity - to a
+ *   consumer that takes its row count from the host (crb_augment_mask_points) the untouched tail is one more frame whose rows land
+ *   behind the total. Count, scan and emit launches plus one for the objects, no atomics: the same bits every call.
+ * ---------------------------------------------------------------------------------------------- */
+int crb_gt_sample_select(const float* gt_boxes, const int32_t* gt_counts, int B, int G, const float* cand,
+                         const int32_t* cand_obj, const int32_t* group_offsets, int S, int K,
+                         const int32_t* obj_offsets, int64_t num_objects, uint8_t* valid, float* out_boxes,
+                         int32_t* new_counts, int32_t* cand_rows, int32_t* paste_counts, void* stream);
+int64_t crb_gt_sample_paste_workspace_bytes(int64_t n_points, int B);
+int crb_gt_sample_paste(const float* points, int64_t n_points, int num_features, const int32_t* frame_offsets, int B,
+                        const float* cand, const int32_t* cand_obj, int S, const uint8_t* valid,
+                        const int32_t* cand_rows, const int32_t* paste_counts, const float* db_points,
+                        const int32_t* obj_offsets, int64_t num_objects, int64_t capacity, float* out_points,
+                        int32_t* new_frame_offsets, void* workspace, int64_t workspace_bytes, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * a4  Sparse 3D convolution: rulebooks + gather-GEMM fwd / dgrad / wgrad
  * replaces: spconv.pytorch.SubMConv3d / SparseConv3d / SparseConvTensor (third-party spconv-cu113 v2.1.21,
  *           not vendored) as used by pcdet/models/backbones_3d/spconv_backbone.py:8-27,77-117,141-157 and
