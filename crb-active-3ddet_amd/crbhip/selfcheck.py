@@ -92,8 +92,22 @@ class WinogradInSitu:
             return
         with torch.no_grad():
             want = F.conv_transpose2d(dy.detach().double(), weight.double(), padding=1)
-            self.records.append(('dgrad', (dy.shape[0], weight.shape[1], weight.shape[0], dy.shape[2], dy.shape[3]),
-                                 self._err(dx.detach(), want)))
+            listed = getattr(dx, '_crb_listed', None)
+            if listed is None:
+                err = self._err(dx.detach(), want)
+            else:
+                # the launch walked the conv-out list of a sparse map (crbhip.bev_blocks): the gradient exists in the listed blocks, the
+                # rest is +0, and its only reader (the gather behind the scatter that made the map) reads the active pixels
+                bl, which = listed
+                assert which == 'out', 'an input-gradient launch walks the conv-out list'
+                mask = bl.pixel_mask('out')                                    # (N,H,W)
+                idx = bl.indices.long()
+                assert bool(mask[idx[:, 0], idx[:, 2], idx[:, 3]].all()), 'an active pixel lies outside the listed blocks'
+                got = dx.detach().permute(0, 2, 3, 1)
+                assert bool((got[~mask] == 0).all()), 'an unlisted block of the input gradient is not zero'
+                ref = want.permute(0, 2, 3, 1)[mask]
+                err = float((got[mask].double() - ref).abs().max() / ref.abs().max().clamp_min(1e-300)) if ref.numel() else 0.0
+            self.records.append(('dgrad', (dy.shape[0], weight.shape[1], weight.shape[0], dy.shape[2], dy.shape[3]), err))
 
     def _wgrad(self, x, dy, dw):
         if not self._take('wgrad'):

@@ -258,6 +258,29 @@ def weights_input_grad4(weight):
     return _weights_conv4(weight, 1)
 
 
+# Sparse first layer (crbhip.bev_blocks, csrc/bev_blocks.hip): a map that carries the block lists of its active pixels
+# (`_crb_bev_blocks`, attached by HeightCompression) is zero outside them, and the launches of the layer that reads it walk the lists
+# instead of the whole map. CRB_WINOGRAD_SPARSE = comma list of the directions that do: f = forward (conv-in list: bit-equal y and
+# slab sums), i = input gradient (conv-out list: bit-equal where it is read, +0 elsewhere), w = weight gradient (wgrad list: equal up
+# to summation order). Empty or 0: the dense launches (A/B). Only the 32 x 128 form (crb_winograd4c_supported) and
+# crb_winograd4_wgrad take a list; every other instance runs dense.
+DEFAULT_SPARSE = 'f,i,w'
+SPARSE = set(v.strip() for v in __import__('os').environ.get('CRB_WINOGRAD_SPARSE', DEFAULT_SPARSE).split(',')
+             if v.strip() and v.strip() != '0')
+
+
+def _listed(x, U, bias, relu):
+    """(BlockLists, 'in' | 'out') when this launch walks a list, else None. `_crb_bev_blocks` on x: x is zero outside the lists'
+    active pixels (forward); `_crb_bev_blocks_out` on x: the OUTPUT is read at the active pixels only (input gradient)."""
+    if bias is not None or relu or not getattr(U, '_crb_c', False):
+        return None
+    for attr, which, flag in (('_crb_bev_blocks', 'in', 'f'), ('_crb_bev_blocks_out', 'out', 'i')):
+        bl = getattr(x, attr, None)
+        if bl is not None and flag in SPARSE and bl.matches(x):
+            return bl, which
+    return None
+
+
 def conv3x3_U4(x, U, bias=None, relu=False):
     """x (N,Cin,H,W) f32 channels_last, U = weights_forward4(...) -> y (N,Cout,H,W) channels_last"""
     require_cuda(x, U)
@@ -268,6 +291,14 @@ def conv3x3_U4(x, U, bias=None, relu=False):
         raise CrbHipError('no Winograd (4) instance for %d -> %d channels on a %d x %d map' % (cin, cout, H, W))
     y = torch.empty((N, cout, H, W), dtype=torch.float32, device=x.device, memory_format=torch.channels_last)
     e0 = _prof_begin()
+    listed = _listed(x, U, bias, relu)
+    if listed is not None:
+        lst, cnt, rest, rcnt = listed[0].conv(listed[1])
+        check(lib.crb_conv3x3_winograd4c_blocks_nhwc(xv.data_ptr(), ptr(U), y.data_ptr(), None, N, H, W, cin, cout, ptr(lst), ptr(cnt),
+                                                     ptr(rest), ptr(rcnt), cur_stream(x.device)), 'crb_conv3x3_winograd4c_blocks_nhwc')
+        _prof_end(e0, 'wino_conv', cin, cout, N, H, W)
+        y._crb_listed = listed
+        return y
     fn = lib.crb_conv3x3_winograd4c_nhwc if getattr(U, '_crb_c', False) else lib.crb_conv3x3_winograd4_nhwc
     check(fn(xv.data_ptr(), ptr(U), y.data_ptr(), N, H, W, cin, cout,
              ptr(bias.contiguous().float()) if bias is not None else None, int(bool(relu)),
@@ -289,6 +320,15 @@ def conv3x3_stats_U4(x, U):
     slabs = lib.crb_winograd4c_stats_slabs(N, H, W) if form_c else lib.crb_winograd4_stats_slabs(N, H, W)
     stats = torch.empty((int(slabs), 2, cout), dtype=torch.float32, device=x.device)
     e0 = _prof_begin()
+    listed = _listed(x, U, None, False)
+    if listed is not None:
+        lst, cnt, rest, rcnt = listed[0].conv(listed[1])
+        check(lib.crb_conv3x3_winograd4c_blocks_nhwc(xv.data_ptr(), ptr(U), y.data_ptr(), ptr(stats), N, H, W, cin, cout, ptr(lst),
+                                                     ptr(cnt), ptr(rest), ptr(rcnt), cur_stream(x.device)),
+              'crb_conv3x3_winograd4c_blocks_nhwc')
+        _prof_end(e0, 'wino_conv', cin, cout, N, H, W)
+        y._crb_listed = listed
+        return y, stats
     fn = lib.crb_conv3x3_winograd4c_stats_nhwc if form_c else lib.crb_conv3x3_winograd4_stats_nhwc
     check(fn(xv.data_ptr(), ptr(U), y.data_ptr(), ptr(stats), N, H, W, cin, cout, cur_stream(x.device)),
           'crb_conv3x3_winograd4_stats_nhwc')
@@ -358,6 +398,13 @@ def conv3x3_wgrad(x, dy, like):
         ws = _WGRAD_WS[key] = torch.empty((nbytes // 4,), dtype=torch.float32, device=x.device)
     so, si, sky, skx = dw.stride()
     e0 = _prof_begin()
+    bl = getattr(x, '_crb_bev_blocks', None)
+    if four and bl is not None and 'w' in SPARSE and bl.matches(x):
+        check(lib.crb_winograd4_wgrad_blocks(xv.data_ptr(), gv.data_ptr(), dw.data_ptr(), so, si, sky, skx, N, H, W, cin, cout,
+                                             ptr(bl.wgrad), ptr(bl.wgrad_count), ptr(ws), ws.numel() * 4, cur_stream(x.device)),
+              'crb_winograd4_wgrad_blocks')
+        _prof_end(e0, 'wino_wgrad', cin, cout, N, H, W)
+        return dw
     fn, name = (lib.crb_winograd4_wgrad, 'crb_winograd4_wgrad') if four else (lib.crb_winograd2_wgrad, 'crb_winograd2_wgrad')
     check(fn(xv.data_ptr(), gv.data_ptr(), dw.data_ptr(), so, si, sky, skx, N, H, W, cin, cout, ptr(ws), ws.numel() * 4,
              cur_stream(x.device)), name)
@@ -365,16 +412,30 @@ def conv3x3_wgrad(x, dy, like):
     return dw
 
 
+def _reattach(ctx, x, dy):
+    """backward of a layer whose input carried block lists: the saved input gets them back (weight gradient), and the gradient that goes
+    into the input-gradient convolution is handed on as a view that names them as the blocks its OUTPUT is read in"""
+    bl = getattr(ctx, 'blocks', None)
+    if bl is None:
+        return dy
+    x._crb_bev_blocks = bl
+    dy = dy.view_as(dy)
+    dy._crb_bev_blocks_out = bl
+    return dy
+
+
 class _Conv3x3(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, weight, bias):
         ctx.save_for_backward(x, weight)
         ctx.has_bias = bias is not None
+        ctx.blocks = getattr(x, '_crb_bev_blocks', None)
         return conv3x3_U2(x, weights_forward2(weight), bias)
 
     @staticmethod
     def backward(ctx, dy):
         x, weight = ctx.saved_tensors
+        dy = _reattach(ctx, x, dy)
         dx = dw = db = None
         wino_dx = ctx.needs_input_grad[0] and supported2(weight.shape[0], weight.shape[1], x.shape[2], x.shape[3])
         if wino_dx:
@@ -416,6 +477,7 @@ class _Conv3x3Stats(torch.autograd.Function):
     def forward(ctx, x, weight):
         require_cuda(x, weight)
         ctx.save_for_backward(x, weight)
+        ctx.blocks = getattr(x, '_crb_bev_blocks', None)
         xv = _nhwc(x.float())
         N, H, W, cin = xv.shape
         cout = weight.shape[0]
@@ -438,6 +500,7 @@ class _Conv3x3Stats(torch.autograd.Function):
     @staticmethod
     def backward(ctx, dy, _ds):
         x, weight = ctx.saved_tensors
+        dy = _reattach(ctx, x, dy)
         dx = dw = None
         if ctx.needs_input_grad[0]:
             if supported2(weight.shape[0], weight.shape[1], x.shape[2], x.shape[3]):

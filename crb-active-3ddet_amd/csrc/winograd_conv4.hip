@@ -33,6 +33,7 @@
 #include <type_traits>
 #include "crb_common.h"
 #include "winograd_split.h"      // split3 and the bf16 / u32 vector types (shared with winograd_wgrad4.hip)
+#include "winograd_blocks.h"     // the spatial block of the 32 x 128 form (shared with bev_blocks.hip, which lists the blocks of a sparse map)
 #include "../../include/crb_hip.h"
 
 typedef float f32x2 __attribute__((ext_vector_type(2)));
@@ -162,6 +163,8 @@ struct Wino4Args {
   int nblocks;               // spatial blocks = ceil(RT / 16) * tw4
   int ncb;                   // cout / 64
   unsigned seq;              // launch sequence number for the busy-CU latch; 0 = ignore g_cu_busy4
+  const int32_t* list;       // winograd4c_kernel only: null, or the ascending spatial blocks to walk (crb_bev_blocks) ...
+  const int32_t* list_count; // ... and how many of them (device memory); every other block of y is left alone
 };
 
 template <int AUX = 0>
@@ -681,7 +684,7 @@ __global__ __launch_bounds__(NT, 1) void winograd4_kernel(Wino4Args a) {
 // and a commuted addition). Same arithmetic as the form above: the outputs are bit-equal.
 // Weight image "c": [Cout/128][Cin/16][xi row][xi][k group][row 128][piece 3][8 bf16] - a lane's three pieces are 48 contiguous bytes.
 namespace c4 {
-constexpr int TB_ROWS = 8, TB_COLS = 4;
+constexpr int TB_ROWS = wino_blocks::C4_TB_ROWS, TB_COLS = wino_blocks::C4_TB_COLS;
 constexpr int WG_K = 128;
 constexpr int U_ROW = 48;
 constexpr int U_XI = 2 * WG_K * U_ROW;         // 12288
@@ -695,10 +698,18 @@ constexpr int RAW_BYTES = RAW_SLOTS * 16;      // 16384
 constexpr int LDS_V = 0, LDS_RAW = 4 * V_PHASE, LDS_BYTES = LDS_RAW + 2 * RAW_BYTES;   // 88832: four V rows (two buffers of two xi rows), two raw blocks
 
 struct UnitPos { int cb, bc, R0, n0, ty0; };
-__device__ __forceinline__ UnitPos unit_at(int u, const Wino4Args& a) {
+__device__ __forceinline__ int sload1(const int32_t* p) {
+  int r;
+  asm volatile("s_load_dword %0, %1, 0x0\n\ts_waitcnt lgkmcnt(0)" : "=s"(r) : "s"(p));
+  return r;
+}
+// unit u = (entry u / ncb of the walk, channel block u % ncb); the walk is every spatial block, or the `listed` blocks of a.list. The
+// copies run one unit past the end of a workgroup's range: such an entry is clamped into the list (nobody reads what it fetches)
+__device__ __forceinline__ UnitPos unit_at(int u, const Wino4Args& a, int listed) {
   UnitPos p;
-  const int tb = u / a.ncb;
-  p.cb = u - tb * a.ncb;
+  const int e = u / a.ncb;
+  p.cb = u - e * a.ncb;
+  const int tb = a.list ? min(max(sload1(a.list + min(e, listed - 1)), 0), a.nblocks - 1) : e;      // (an entry never leaves the map)
   const int br = tb / a.tw4;
   p.bc = tb - br * a.tw4;
   p.R0 = br * TB_ROWS;
@@ -734,7 +745,8 @@ __global__ __launch_bounds__(NT, 1) void winograd4c_kernel(Wino4Args a) {
                "a242", "a243", "a244", "a245", "a246", "a247", "a248", "a249", "a250", "a251", "a252", "a253", "a254", "a255");
 
   // ---- the unit range of this workgroup (busy-CU latch as in the forms above)
-  const int nunits = a.nblocks * a.ncb;
+  const int listed = a.list ? min(max(*a.list_count, 0), a.nblocks) : a.nblocks;      // (a list: the walk is as long as the list)
+  const int nunits = listed * a.ncb;
   int G = gridDim.x;
   if (a.seq) {
     if (T == 0) {
@@ -779,7 +791,7 @@ __global__ __launch_bounds__(NT, 1) void winograd4c_kernel(Wino4Args a) {
   auto px_pos = [](int x) { return (x == 1 || x == 2) ? 3 - x : (x == 7 || x == 8) ? 15 - x : x; };
   int raw_rd[3];
   auto raw_base = [&](int u) {
-    const UnitPos p = c4::unit_at(u, a);
+    const UnitPos p = c4::unit_at(u, a, listed);
     const int rows_a = min(TB_ROWS, a.th - p.ty0);
     const int lr = 2 * t_tr + (t_tr >= rows_a ? 2 : 0);
     const int b0 = t_h ? 2 : 0, b1 = t_h ? 1 : 2, b2 = t_h ? 3 : 1;
@@ -795,7 +807,7 @@ __global__ __launch_bounds__(NT, 1) void winograd4c_kernel(Wino4Args a) {
   const float* rsrc[4];
   unsigned rstep = 0;
   auto raw_sources = [&](int u) {
-    const UnitPos p = c4::unit_at(u, a);
+    const UnitPos p = c4::unit_at(u, a, listed);
     const int rows_a = min(TB_ROWS, a.th - p.ty0);
     const int limit_a = 2 * rows_a + 2;
     rstep = 0;
@@ -928,7 +940,7 @@ __global__ __launch_bounds__(NT, 1) void winograd4c_kernel(Wino4Args a) {
     }
   };
   auto unit_epilogue = [&]() __attribute__((always_inline)) {
-    const UnitPos eu = c4::unit_at(e_unit, a);
+    const UnitPos eu = c4::unit_at(e_unit, a, listed);
     const int tr = l31 >> 2, tc = l31 & 3;
     const int Rg = eu.R0 + tr;
     const int tx = eu.bc * TB_COLS + tc;
@@ -1644,11 +1656,38 @@ int crbhip_wino4_cu_busy_set(int cus, hipStream_t stream) {
   return CRB_OK;
 }
 
+// +0 into the blocks of y (and their statistics slabs) that a listed launch of winograd4c_kernel does not walk: what the dense launch
+// writes there when the block's input patch is all zero (accumulators start at +0, sums of +-0 products stay +0)
+__global__ __launch_bounds__(256) void winograd4c_fill_kernel(float* __restrict__ y, float* __restrict__ stats, int N, int H, int W, int cout,
+                                                              int th, int RT, int tw4, const int32_t* __restrict__ rest,
+                                                              const int32_t* __restrict__ rest_count, int nblocks) {
+  const int n_rest = min(max(*rest_count, 0), nblocks);
+  const int c4n = cout / 4, px_items = c4::TB_COLS * 2 * c4n, items = c4::TB_ROWS * 2 * px_items;
+  for (int j = blockIdx.x; j < n_rest; j += gridDim.x) {
+    const int tb = rest[j];
+    if ((unsigned)tb >= (unsigned)nblocks) continue;
+    const int br = tb / tw4, bc = tb - br * tw4;
+    for (int i = threadIdx.x; i < items; i += 256) {
+      const int prow = i / px_items, rem = i - prow * px_items;
+      const int px = rem / c4n, q = rem - px * c4n;
+      const int R = br * c4::TB_ROWS + (prow >> 1);
+      const int n = R / th, oy = 2 * (R - n * th) + (prow & 1), ox = bc * (c4::TB_COLS * 2) + px;
+      if (R < RT && oy < H && ox < W)
+        *reinterpret_cast<f32x4*>(y + (((int64_t)n * H + oy) * W + ox) * cout + 4 * q) = (f32x4){0.f, 0.f, 0.f, 0.f};
+    }
+    if (stats)
+      for (int i = threadIdx.x; i < 2 * c4n; i += 256)
+        *reinterpret_cast<f32x4*>(stats + (int64_t)tb * 2 * cout + 4 * i) = (f32x4){0.f, 0.f, 0.f, 0.f};
+  }
+}
+
+// blocks: null (every block), or {list, count, rest, rest count} of crb_bev_blocks: the kernel walks `list`, the fill covers `rest`
 static int winograd4c_launch(const float* x, const void* U, float* y, int N, int H, int W, int cin, int cout, const float* bias, int relu,
-                             void* stream, float* stats) {
+                             void* stream, float* stats, const int32_t* const* blocks = nullptr) {
   if (N <= 0 || H <= 0 || W <= 0) return CRB_ERR_ARG;
   if (!crb_winograd4c_supported(cin, cout, H, W)) return CRB_ERR_UNSUPPORTED;
   Wino4Args a;
+  a.list = blocks ? blocks[0] : nullptr; a.list_count = blocks ? blocks[1] : nullptr;
   a.x = x; a.U = (const unsigned char*)U; a.y = y; a.bias = bias; a.stats = stats;
   a.N = N; a.H = H; a.W = W; a.cin = cin; a.cout = cout; a.relu = relu;
   a.th = (H + 1) / 2; a.tw = (W + 1) / 2;
@@ -1671,6 +1710,12 @@ static int winograd4c_launch(const float* x, const void* U, float* y, int N, int
   const int64_t grid = units < n_cu ? units : n_cu;
   unsigned seq = (g_dev_seq4[dev].fetch_add(1, std::memory_order_relaxed) + 1) & 0xffffffu;
   a.seq = (grid == n_cu) ? (seq ? seq : 1) : 0;
+  if (blocks) {
+    const int64_t fgrid = nb < 8192 ? nb : 8192;
+    hipLaunchKernelGGL(winograd4c_fill_kernel, dim3((unsigned)fgrid), dim3(256), 0, (hipStream_t)stream, y, stats, N, H, W, cout, a.th, a.RT,
+                       a.tw4, blocks[2], blocks[3], a.nblocks);
+    CRB_CHECK_LAUNCH();
+  }
   hipLaunchKernelGGL(winograd4c_kernel, dim3((unsigned)grid), dim3(NT), c4::LDS_BYTES, (hipStream_t)stream, a);
   CRB_CHECK_LAUNCH();
   return CRB_OK;
@@ -1693,11 +1738,22 @@ extern "C" int crb_conv3x3_winograd4c_stats_nhwc(const float* x, const void* U, 
   return winograd4c_launch(x, U, y, N, H, W, cin, cout, nullptr, 0, stream, stats);
 }
 
+// The bias-free, ReLU-free convolution over the listed spatial blocks only (training: forward of a layer whose input is zero outside
+// the conv-in list, input gradient of a layer whose input gradient is read inside the conv-out list only); stats may be null
+extern "C" int crb_conv3x3_winograd4c_blocks_nhwc(const float* x, const void* U, float* y, float* stats, int N, int H, int W, int cin,
+                                                  int cout, const int32_t* list, const int32_t* count, const int32_t* rest,
+                                                  const int32_t* rest_count, void* stream) {
+  if (!list || !count || !rest || !rest_count) return CRB_ERR_ARG;
+  const int32_t* const blocks[4] = {list, count, rest, rest_count};
+  return winograd4c_launch(x, U, y, N, H, W, cin, cout, nullptr, 0, stream, stats, blocks);
+}
+
 static int winograd4_launch(const float* x, const void* U, float* y, int N, int H, int W, int cin, int cout, const float* bias, int relu,
                             void* stream, float* stats) {
   if (N <= 0 || H <= 0 || W <= 0) return CRB_ERR_ARG;
   if (!crb_winograd4_supported(cin, cout, H, W)) return CRB_ERR_UNSUPPORTED;
   Wino4Args a;
+  a.list = nullptr; a.list_count = nullptr;
   a.x = x; a.U = (const unsigned char*)U; a.y = y; a.bias = bias; a.stats = stats;
   a.N = N; a.H = H; a.W = W; a.cin = cin; a.cout = cout; a.relu = relu;
   a.th = (H + 1) / 2; a.tw = (W + 1) / 2;

@@ -33,6 +33,7 @@
 #include <utility>
 #include "crb_common.h"
 #include "winograd_split.h"
+#include "winograd_blocks.h"     // the tile chunk as bev_blocks.hip sees it (chunk lists of a sparse map)
 #include "../../include/crb_hip.h"
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
@@ -63,7 +64,15 @@ struct Wg4Args {
   int nchunks;         // N * rp * tc4
   int nci, nco;        // channel blocks of 128
   int nranges;         // K ranges (multiple of 8)
+  const int32_t* list;        // LIST instances: the ascending chunks to walk (crb_bev_blocks: chunks whose x patch holds an active pixel) ...
+  const int32_t* list_count;  // ... and how many of them (device memory)
 };
+
+__device__ __forceinline__ int sload1(const int32_t* p) {
+  int r;
+  asm volatile("s_load_dword %0, %1, 0x0\n\ts_waitcnt lgkmcnt(0)" : "=s"(r) : "s"(p));
+  return r;
+}
 
 struct ChunkPos { int n, p, bc; };
 __device__ __forceinline__ void chunk_next(ChunkPos& c, const Wg4Args& a) {
@@ -115,8 +124,12 @@ __device__ __forceinline__ void reg_anchor(float& x) { asm volatile("" : "+v"(x)
 // TOUCH: every wave also reads one dword of each 128-byte line of the chunk AFTER the one it requests (8 loads per chunk whose values
 // nobody uses): the maps are first-touch HBM lines, and one chunk of lead (64 MFMAs) does not cover that latency under load; the
 // pixels themselves then come from L2
-template <int MODE, bool TOUCH, int LP2 = 3>
+// LIST: the ranges split a.list instead of all chunks and every chunk position is decoded from its list entry (a skipped chunk adds
+// exact zeros, so only the summation order moves with the range boundaries); the prefetch touches assume the next chunk of a row
+// is the neighbour: no LIST instance with TOUCH
+template <int MODE, bool TOUCH, int LP2 = 3, bool LIST = false>
 __global__ __launch_bounds__(NT, 1) void winograd4_wgrad_kernel(Wg4Args a) {
+  static_assert(!(LIST && TOUCH), "the prefetch touches follow chunk_next");
   extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
   unsigned char* const Vimg = lds;
   unsigned char* const Mimg = lds + IMG_BYTES;
@@ -145,8 +158,9 @@ __global__ __launch_bounds__(NT, 1) void winograd4_wgrad_kernel(Wg4Args a) {
   if (range >= a.nranges) return;
   const int xr = sub & 3, blk = sub >> 2;      // xi row i of the 4 x 4 Winograd domain
   const int cib = blk / a.nco, cob = blk - cib * a.nco;
-  const int c_first = (int)((int64_t)range * a.nchunks / a.nranges);
-  const int c_end = (int)((int64_t)(range + 1) * a.nchunks / a.nranges);
+  const int nwalk = LIST ? min(max(*a.list_count, 0), a.nchunks) : a.nchunks;
+  const int c_first = (int)((int64_t)range * nwalk / a.nranges);
+  const int c_end = (int)((int64_t)(range + 1) * nwalk / a.nranges);
   const int total = c_end - c_first;          // (0 with more ranges than chunks: a zero partial)
 
   static_for<256>([](auto r) { acc_zero<decltype(r)::value>(); });
@@ -196,8 +210,20 @@ __global__ __launch_bounds__(NT, 1) void winograd4_wgrad_kernel(Wg4Args a) {
       }
     }
   };
+  int walk = c_first;                          // LIST: the list entry cp came from
+  auto at_entry = [&](int e) __attribute__((always_inline)) {     // cp = chunk of list entry e (clamped: requests past the end of the list
+                                                                  // fetch its last chunk, nobody reads them)
+    const int ch = min(max(sload1(a.list + min(e, nwalk - 1)), 0), a.nchunks - 1);
+    const int rows = ch / a.tc4;
+    cp.bc = ch - rows * a.tc4;
+    cp.n = rows / a.rp;
+    cp.p = rows - cp.n * a.rp;
+  };
   auto advance = [&]() __attribute__((always_inline)) {       // cp -> the next chunk; the pointers follow
-    if (cp.bc + 1 < a.tc4) {
+    if (LIST) {
+      at_entry(++walk);
+      set_rows();
+    } else if (cp.bc + 1 < a.tc4) {
       ++cp.bc;
 #pragma unroll
       for (int r = 0; r < 2; ++r)
@@ -414,7 +440,8 @@ __global__ __launch_bounds__(NT, 1) void winograd4_wgrad_kernel(Wg4Args a) {
 
   if (total > 0) {
     // ---- prologue: chunk 0 -> t, m -> xi 0, 1 of the images; chunk 1 requested
-    {
+    if (LIST) at_entry(c_first);
+    else {
       const int rows = c_first / a.tc4;
       cp.bc = c_first - rows * a.tc4;
       cp.n = rows / a.rp;
@@ -555,8 +582,9 @@ extern "C" int64_t crb_winograd4_wgrad_workspace_bytes(int cin, int cout) {
 
 // x (N,H,W,Cin), dy (N,H,W,Cout) f32 NHWC -> dw = gradient of the nn.Conv2d weight (Cout,Cin,3,3), written with the element
 // strides (so, si, sky, skx) of that tensor. workspace: crb_winograd4_wgrad_workspace_bytes(cin, cout).
-extern "C" int crb_winograd4_wgrad(const float* x, const float* dy, float* dw, int64_t so, int64_t si, int64_t sky, int64_t skx,
-                                   int N, int H, int W, int cin, int cout, void* workspace, int64_t workspace_bytes, void* stream) {
+static int wgrad4_launch(const float* x, const float* dy, float* dw, int64_t so, int64_t si, int64_t sky, int64_t skx, int N, int H, int W,
+                         int cin, int cout, void* workspace, int64_t workspace_bytes, void* stream, const int32_t* list,
+                         const int32_t* list_count) {
   if (N <= 0 || H <= 0 || W <= 0) return CRB_ERR_ARG;
   if (!crb_winograd4_wgrad_supported(cin, cout, H, W)) return CRB_ERR_UNSUPPORTED;
   if (workspace_bytes < crb_winograd4_wgrad_workspace_bytes(cin, cout) || !workspace) return CRB_ERR_WORKSPACE;
@@ -573,10 +601,11 @@ extern "C" int crb_winograd4_wgrad(const float* x, const float* dy, float* dw, i
   }
   Wg4Args a;
   a.x = x; a.dy = dy; a.part = (float*)workspace; a.zero = zero_page;
+  a.list = list; a.list_count = list_count;
   a.N = N; a.H = H; a.W = W; a.cin = cin; a.cout = cout;
   a.th = (H + 1) / 2; a.tw = (W + 1) / 2;
-  a.tc4 = (a.tw + 3) / 4;
-  a.rp = (a.th + 3) / 4;
+  a.tc4 = (a.tw + wino_blocks::WG4_CH_COLS - 1) / wino_blocks::WG4_CH_COLS;
+  a.rp = (a.th + wino_blocks::WG4_CH_ROWS - 1) / wino_blocks::WG4_CH_ROWS;
   const int64_t nch = (int64_t)N * a.rp * a.tc4;
   if (nch >= (1LL << 30)) return CRB_ERR_ARG;
   a.nchunks = (int)nch;
@@ -592,7 +621,8 @@ extern "C" int crb_winograd4_wgrad(const float* x, const float* dy, float* dw, i
   if (g_wgrad4_mode == 5) kern = winograd4_wgrad_kernel<0, false, 4>;
   if (g_wgrad4_mode == 6) kern = winograd4_wgrad_kernel<0, false, 10>;
 #endif
-  const unsigned bit = 1u << (g_wgrad4_mode & 7);
+  if (list) kern = winograd4_wgrad_kernel<0, false, 3, true>;
+  const unsigned bit = list ? (1u << 8) : 1u << (g_wgrad4_mode & 7);
   if (!(attr_done[dev].load(std::memory_order_acquire) & bit)) {
     CRB_HIP(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES));
     attr_done[dev].fetch_or(bit, std::memory_order_release);
@@ -603,4 +633,17 @@ extern "C" int crb_winograd4_wgrad(const float* x, const float* dy, float* dw, i
                      (const float*)workspace, a.nranges, a.nci * 2, a.nco * 2, dw, so, si, sky, skx, cin, cout);
   CRB_CHECK_LAUNCH();
   return CRB_OK;
+}
+
+extern "C" int crb_winograd4_wgrad(const float* x, const float* dy, float* dw, int64_t so, int64_t si, int64_t sky, int64_t skx,
+                                   int N, int H, int W, int cin, int cout, void* workspace, int64_t workspace_bytes, void* stream) {
+  return wgrad4_launch(x, dy, dw, so, si, sky, skx, N, H, W, cin, cout, workspace, workspace_bytes, stream, nullptr, nullptr);
+}
+
+// the same gradient over the listed chunks only: x is zero in the patch of every other chunk (crb_bev_blocks: the wgrad list)
+extern "C" int crb_winograd4_wgrad_blocks(const float* x, const float* dy, float* dw, int64_t so, int64_t si, int64_t sky, int64_t skx,
+                                          int N, int H, int W, int cin, int cout, const int32_t* list, const int32_t* count,
+                                          void* workspace, int64_t workspace_bytes, void* stream) {
+  if (!list || !count) return CRB_ERR_ARG;
+  return wgrad4_launch(x, dy, dw, so, si, sky, skx, N, H, W, cin, cout, workspace, workspace_bytes, stream, list, count);
 }

@@ -915,6 +915,33 @@ int64_t crb_winograd4c_stats_slabs(int N, int H, int W);
 int crb_conv3x3_winograd4c_stats_nhwc(const float* x, const void* U, float* y, float* stats, int N, int H, int W, int cin,
                                       int cout, void* stream);
 
+/* Block lists of a sparse BEV map for the two kernels above and crb_winograd4_wgrad (csrc/bev_blocks.hip, csrc/winograd_blocks.h).
+ * replaces: nothing in the reference, which runs cuDNN over the whole scattered map
+ *           (pcdet/models/backbones_2d/map_to_bev/height_compression.py:20-26 feeding base_bev_backbone.py:24-41); here the first
+ *           3x3 layer skips the blocks of its 88 %-zero input that cannot change the result.
+ * indices (n,4) int32 rows (b, z, y, x): the rows crb_sparse_to_dense_nhwc scatters; a pixel (b, y, x) named by a row is ACTIVE.
+ * layout of out (int32, crb_bev_blocks_ints(N, H, W) entries, device memory; nothing is read back):
+ *   [0..7]  counts: conv-in list, conv-out list, wgrad list, rest of conv-in, rest of conv-out, 0, 0, 0
+ *   then five ascending lists: conv-in (nb), rest of conv-in (nb), conv-out (nb), rest of conv-out (nb), wgrad (nc); a list's entries
+ *   behind its count are unspecified; behind the lists the builder's flag bytes.
+ *   conv-in:  spatial blocks of crb_conv3x3_winograd4c_nhwc (8 tile rows over N * ceil(H / 2) x 4 tile columns, nb of them, numbered
+ *             row-major) with an active pixel within one pixel of their outputs: every other block of y is +0 when x is zero outside
+ *             the active pixels;  conv-out: blocks that hold an active pixel;  rest: the blocks not listed (what a fill has to clear);
+ *   wgrad:    chunks of crb_winograd4_wgrad (4 x 4 tiles of one image, nc = N * ceil(th / 4) * ceil(tw / 4), numbered (n, row, column))
+ *             with an active pixel within one pixel of their 8 x 8 pixels.
+ * crb_bev_blocks_geometry: host array of 12: nb, nc, th, tw, block columns, chunk rows per image, chunk columns, tile size, block tile
+ * rows / columns, chunk tile rows / columns. Marking: one thread per index, plain byte stores; compaction: an ordered scan. No atomics. */
+int crb_bev_blocks_geometry(int N, int H, int W, int32_t* geom);
+int64_t crb_bev_blocks_ints(int N, int H, int W);
+int crb_bev_blocks(const int32_t* indices, int64_t n, int N, int H, int W, int32_t* out, int64_t out_ints, void* stream);
+/* crb_conv3x3_winograd4c_nhwc without bias / ReLU (stats null) or crb_conv3x3_winograd4c_stats_nhwc over the blocks of `list` only
+ * (*count of them); the blocks of `rest` (and their statistics slabs) are filled with +0 by a small launch in front. With the
+ * conv-in list of a map that is zero outside its active pixels, y and stats are bit-equal to the dense launch; with the conv-out
+ * list the listed blocks are (the input gradient of that map, which is read at the active pixels only). */
+int crb_conv3x3_winograd4c_blocks_nhwc(const float* x, const void* U, float* y, float* stats, int N, int H, int W, int cin,
+                                       int cout, const int32_t* list, const int32_t* count, const int32_t* rest,
+                                       const int32_t* rest_count, void* stream);
+
 /* a7 backward: weight gradient of the same convolution in the Winograd domain (csrc/winograd_wgrad.hip):
  * dU[xi][ci][co] = sum over tiles of (B^T d B)[xi][ci] * (A dY A^T)[xi][co] as 16 MFMA GEMMs whose two operands are both
  * produced by transforms inside the kernel, partial sums per range of tiles in the workspace, then dW = G^T dU G added up in
@@ -941,6 +968,12 @@ int crb_winograd4_wgrad_supported(int cin, int cout, int H, int W);
 int64_t crb_winograd4_wgrad_workspace_bytes(int cin, int cout);
 int crb_winograd4_wgrad(const float* x, const float* dy, float* dw, int64_t so, int64_t si, int64_t sky, int64_t skx,
                         int N, int H, int W, int cin, int cout, void* workspace, int64_t workspace_bytes, void* stream);
+/* the same gradient over the chunks of `list` only (the wgrad list of crb_bev_blocks: x is zero in the patch of every other chunk).
+ * The K ranges split the list instead of all chunks: equal to crb_winograd4_wgrad up to the order of the f32 sums, and bit-equal
+ * from call to call. */
+int crb_winograd4_wgrad_blocks(const float* x, const float* dy, float* dw, int64_t so, int64_t si, int64_t sky, int64_t skx,
+                               int N, int H, int W, int cin, int cout, const int32_t* list, const int32_t* count,
+                               void* workspace, int64_t workspace_bytes, void* stream);
 
 /* Transposed convolutions with kernel = stride as row GEMMs on the bf16 matrix pipe (csrc/rows_gemm4.hip): a channels_last map is
  * the row matrix (pixels x channels), so ConvTranspose2d(cin -> cout, k = s, stride = s, no padding, no bias, groups 1) is
