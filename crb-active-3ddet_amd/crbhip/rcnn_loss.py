@@ -71,6 +71,44 @@ def rcnn_loss(rcnn_cls, rcnn_reg, cls_labels, reg_valid_mask, rois, gt_of_rois, 
                            f(rois).view(n, 7), f(gt_of_rois).view(n, c), f(gt_of_rois_src).view(n, c), cfg)
 
 
+IOU_LOSS_KINDS = {'BinaryCrossEntropy': 0, 'L2': 1, 'smoothL1': 2}       # CRB_IOU_LOSS_* of include/crb_hip.h
+
+
+class _RcnnIouLoss(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, rcnn_iou, labels, kind, weight):
+        n, dev = int(rcnn_iou.numel()), rcnn_iou.device
+        buf = torch.empty((2,), dtype=torch.float32, device=dev)
+        d_iou = torch.empty((n,), dtype=torch.float32, device=dev)
+        check(lib.crb_rcnn_iou_loss(ptr(rcnn_iou), ptr(labels), n, int(kind), float(weight), ptr(buf), ptr(d_iou), cur_stream(dev)),
+              'crb_rcnn_iou_loss')
+        ctx.save_for_backward(d_iou)
+        ctx.shape = rcnn_iou.shape
+        loss, valid = buf[0], buf[1]
+        ctx.mark_non_differentiable(valid)
+        ctx.set_materialize_grads(False)
+        return loss, valid
+
+    @staticmethod
+    def backward(ctx, g, _gv):
+        if g is None:
+            return None, None, None, None
+        return (ctx.saved_tensors[0] * g).view(ctx.shape), None, None, None
+
+
+def rcnn_iou_loss(rcnn_iou, labels, kind, weight):
+    """SECONDHead.get_box_iou_layer_loss (second_head.py:153-178) as one launch: rcnn_iou (n,1) / (n) logits, labels (n) soft IoU
+    targets (< 0 = ignored), kind in IOU_LOSS_KINDS -> (rcnn_loss_iou scalar with the graph, number of valid rows)"""
+    require_cuda(rcnn_iou, labels)
+    if kind not in IOU_LOSS_KINDS:
+        raise CrbHipError('crb_rcnn_iou_loss: IOU_LOSS %r is not one of %s' % (kind, sorted(IOU_LOSS_KINDS)))
+    if rcnn_iou.numel() != labels.numel():
+        raise CrbHipError('crb_rcnn_iou_loss: %d logits for %d labels' % (rcnn_iou.numel(), labels.numel()))
+    n = int(labels.numel())
+    return _RcnnIouLoss.apply(rcnn_iou.contiguous().float().view(n), labels.detach().contiguous().float().view(n),
+                              IOU_LOSS_KINDS[kind], float(weight))
+
+
 class _RcnnLossPerFrame(torch.autograd.Function):
     @staticmethod
     def forward(ctx, rcnn_cls, rcnn_reg, labels, reg_valid, rois, gt_local, gt_src, B, cfg):

@@ -232,6 +232,44 @@ __global__ __launch_bounds__(TPB) void rcnn_loss_frames_kernel(RcnnArgs a, int B
   }
 }
 
+// IoU-regression loss of SECONDHead (second_head.py:153-178): per-RoI term of the chosen kind against the soft IoU label, rows with
+// a negative label ignored, sum / max(valid, 1) * weight, and its gradient w.r.t. the logits. kind 0 = BinaryCrossEntropy (with
+// logits: (1 - y) x - log_sigmoid(x), gradient sigmoid(x) - y), 1 = L2 ((x - y)^2), 2 = smoothL1 (knee 1/9).
+__global__ __launch_bounds__(TPB) void rcnn_iou_loss_kernel(const float* __restrict__ iou, const float* __restrict__ labels, int n, int kind,
+                                                            float weight, float* __restrict__ out, float* __restrict__ d_iou) {
+  __shared__ float sh[TPB / 64];
+  float nv = 0.f;
+  for (int i = threadIdx.x; i < n; i += TPB) nv += labels[i] >= 0.f ? 1.f : 0.f;
+  const float n_valid = block_sum(nv, sh);                                  // (an integer below 2^24: exact in any order)
+  const float den = fmaxf(n_valid, 1.f), beta = 1.0f / 9.0f;
+  float s = 0.f;
+  for (int i = threadIdx.x; i < n; i += TPB) {
+    const float y = labels[i], x = iou[i];
+    float l = 0.f, g = 0.f;
+    if (y >= 0.f) {
+      if (kind == 0) {
+        l = ((1.f - y) * x - fminf(x, 0.f)) + log1pf(expf(-fabsf(x)));
+        g = 1.0f / (1.0f + expf(-x)) - y;
+      } else if (kind == 1) {
+        const float d = x - y;
+        l = d * d;
+        g = 2.f * d;
+      } else {
+        const float d = x - y, m = fabsf(d);
+        l = m < beta ? 0.5f * m * m / beta : m - 0.5f * beta;
+        g = m < beta ? d / beta : (d > 0.f ? 1.f : -1.f);
+      }
+    }
+    s += l;
+    d_iou[i] = g * (weight / den);
+  }
+  const float t = block_sum(s, sh);
+  if (threadIdx.x == 0) {
+    out[0] = t / den * weight;
+    out[1] = n_valid;
+  }
+}
+
 __global__ __launch_bounds__(256) void scale_rows_kernel(const float* __restrict__ src, int64_t total, int64_t per_frame, const float* __restrict__ g,
                                                          float* __restrict__ dst) {
   const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
@@ -440,6 +478,15 @@ extern "C" int crb_rcnn_loss(const float* rcnn_cls, const float* rcnn_reg, const
   a.w_cls = cfg->cls_weight; a.w_reg = cfg->reg_weight; a.w_corner = cfg->corner_weight;
   a.out = loss; a.d_cls = d_cls; a.d_reg = d_reg; a.reg_targets = reg_targets;
   hipLaunchKernelGGL(rcnn_loss_kernel, dim3(1), dim3(TPB), 0, (hipStream_t)stream, a);
+  CRB_CHECK_LAUNCH();
+  return CRB_OK;
+}
+
+extern "C" int crb_rcnn_iou_loss(const float* rcnn_iou, const float* labels, int64_t n, int kind, float weight, float* loss, float* d_iou,
+                                 void* stream) {
+  if (n < 0 || n >= (1LL << 24) || kind < CRB_IOU_LOSS_BCE || kind > CRB_IOU_LOSS_SMOOTH_L1 || !loss) return CRB_ERR_ARG;
+  if (n > 0 && (!rcnn_iou || !labels || !d_iou)) return CRB_ERR_ARG;
+  hipLaunchKernelGGL(rcnn_iou_loss_kernel, dim3(1), dim3(TPB), 0, (hipStream_t)stream, rcnn_iou, labels, (int)n, kind, weight, loss, d_iou);
   CRB_CHECK_LAUNCH();
   return CRB_OK;
 }

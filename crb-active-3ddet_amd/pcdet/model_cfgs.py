@@ -58,6 +58,29 @@ def second_cfg(kind='kitti'):
     })
 
 
+def second_iou_cfg():
+    """values of tools/cfgs/kitti_models/second_iou.yaml: the KITTI SECOND trunk + SECONDHead (7 x 7 BEV grid pooling on the
+    512-channel stride-8 map, IoU branch), boxes re-scored by the predicted IoU"""
+    c = second_cfg('kitti')
+    m = c.MODEL
+    m.NAME = 'SECONDNetIoU'
+    m.ROI_HEAD = EasyDict({
+        'NAME': 'SECONDHead', 'CLASS_AGNOSTIC': True, 'SHARED_FC': [256, 256], 'IOU_FC': [256, 256], 'DP_RATIO': 0.3,
+        'NMS_CONFIG': {
+            'TRAIN': {'NMS_TYPE': 'nms_gpu', 'MULTI_CLASSES_NMS': False, 'NMS_PRE_MAXSIZE': 9000,
+                      'NMS_POST_MAXSIZE': 512, 'NMS_THRESH': 0.8},
+            'TEST': {'NMS_TYPE': 'nms_gpu', 'MULTI_CLASSES_NMS': False, 'NMS_PRE_MAXSIZE': 1024,
+                     'NMS_POST_MAXSIZE': 100, 'NMS_THRESH': 0.7}},
+        'ROI_GRID_POOL': {'GRID_SIZE': 7, 'IN_CHANNEL': 512, 'DOWNSAMPLE_RATIO': 8},
+        'TARGET_CONFIG': {'BOX_CODER': 'ResidualCoder', 'ROI_PER_IMAGE': 128, 'FG_RATIO': 0.5,
+                          'SAMPLE_ROI_BY_EACH_CLASS': True, 'CLS_SCORE_TYPE': 'roi_iou', 'CLS_FG_THRESH': 0.75,
+                          'CLS_BG_THRESH': 0.25, 'CLS_BG_THRESH_LO': 0.1, 'HARD_BG_RATIO': 0.8, 'REG_FG_THRESH': 0.55},
+        'LOSS_CONFIG': {'IOU_LOSS': 'BinaryCrossEntropy',
+                        'LOSS_WEIGHTS': {'rcnn_iou_weight': 1.0, 'code_weights': [1.0, 1.0, 1.0, 1.0, 1.0, 1.0, 1.0]}}})
+    c.OPTIMIZATION.update({'DECAY_STEP_LIST': [35, 45], 'LR_DECAY': 0.1, 'LR_CLIP': 0.0000001, 'LR_WARMUP': False, 'WARMUP_EPOCH': 1})
+    return c
+
+
 def pv_rcnn_cfg(kind='kitti'):
     """values of tools/cfgs/active-kitti_models/pv_rcnn_active_crb.yaml; kind='waymo': the differences of
     tools/cfgs/active-waymo_models/pv_rcnn_active_crb.yaml applied on top (anchors, 4096 keypoints, bev/x_conv3/x_conv4/

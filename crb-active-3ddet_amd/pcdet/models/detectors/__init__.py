@@ -12,6 +12,12 @@ try:
 except ImportError:   # PV-RCNN pieces land after SECOND
     pass
 
+try:
+    from .second_net_iou import SECONDNetIoU
+    __all__['SECONDNetIoU'] = SECONDNetIoU
+except ImportError:
+    pass
+
 
 def build_detector(model_cfg, num_class, dataset):
     return __all__[model_cfg.NAME](model_cfg=model_cfg, num_class=num_class, dataset=dataset)

@@ -3,6 +3,8 @@ try:
     from .roi_head_template import RoIHeadTemplate
     from .pvrcnn_head import PVRCNNHead
     from .partA2_head import PartA2FCHead
-    __all__.update({'RoIHeadTemplate': RoIHeadTemplate, 'PVRCNNHead': PVRCNNHead, 'PartA2FCHead': PartA2FCHead})
+    from .second_head import SECONDHead
+    __all__.update({'RoIHeadTemplate': RoIHeadTemplate, 'PVRCNNHead': PVRCNNHead, 'PartA2FCHead': PartA2FCHead,
+                    'SECONDHead': SECONDHead})
 except ImportError:
     pass

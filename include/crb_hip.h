@@ -792,6 +792,16 @@ int crb_rcnn_loss_per_frame(const float* rcnn_cls, const float* rcnn_reg, const 
                             const int64_t* reg_valid_mask, const float* rois, const float* gt_of_rois, const float* gt_of_rois_src,
                             int gt_row_stride, int64_t n, int B, const CrbRcnnLossCfg* cfg, float* loss_frames, float* d_cls, float* d_reg,
                             float* reg_targets, void* stream);
+/* crb_rcnn_iou_loss replaces SECONDHead.get_box_iou_layer_loss (pcdet/models/roi_heads/second_head.py:153-178; ~12 torch launches
+ *   forward and as many backward): rcnn_iou (n) logits, labels (n) f32 soft IoU targets of CLS_SCORE_TYPE roi_iou (< 0 = ignored),
+ *   kind = LOSS_CONFIG.IOU_LOSS (BinaryCrossEntropy with logits / L2 / smoothL1 with the knee 1/9 of loss_utils.py:75-131), weight =
+ *   LOSS_WEIGHTS.rcnn_iou_weight -> loss[2] = {rcnn_loss_iou = sum over the valid rows / max(valid, 1) * weight, valid rows},
+ *   d_iou (n) = d rcnn_loss_iou / d rcnn_iou (0 on ignored rows). One workgroup, sums in a fixed order: bit-reproducible. */
+#define CRB_IOU_LOSS_BCE 0
+#define CRB_IOU_LOSS_L2 1
+#define CRB_IOU_LOSS_SMOOTH_L1 2
+int crb_rcnn_iou_loss(const float* rcnn_iou, const float* labels, int64_t n, int kind, float weight, float* loss, float* d_iou,
+                      void* stream);
 /* backward of the per-frame losses above (replaces autograd's broadcast multiply of the per-row gradients by the (B,) upstream
  * gradient): src (rows, width) -> dst = src * g[row / (rows / frames)]. */
 int crb_scale_rows_per_frame(const float* src, int64_t rows, int width, int frames, const float* g, float* dst, void* stream);
@@ -1031,6 +1041,27 @@ int crb_bev_interpolate_forward(const float* bev, int B, int H, int W, int C, co
                                 float y_min, float voxel_x, float voxel_y, float bev_stride, float* out, void* stream);
 int crb_bev_interpolate_backward(const float* dout, int B, int H, int W, int C, const float* keypoints, int64_t M, float x_min,
                                  float y_min, float voxel_x, float voxel_y, float bev_stride, float* dbev, void* stream);
+
+/* rotated grid pooling of the BEV map under the first-stage proposals (csrc/roi_bev_pool.hip)
+ * replaces: SECONDHead.roi_grid_pool (pcdet/models/roi_heads/second_head.py:53-110): per frame theta from the RoI (:79-92),
+ *           affine_grid (:95-98) and grid_sample (:100-103) over a (R, C, H, W) expand of the NCHW map, torch.cat over the frames.
+ * bev (B,H,W,C) f32 NHWC (= the channels_last (B,C,H,W) map; never transposed), C % 4 == 0, H, W >= 2, 16-byte aligned;
+ * rois (B * R, roi_row_stride >= 7) f32 [x, y, z, dx, dy, dz, rz, ...], R per frame, frame of row n = n / R; cell_x / cell_y =
+ * VOXEL_SIZE[0 / 1] * DOWNSAMPLE_RATIO. Per RoI, with W1 = W - 1, H1 = H - 1:
+ *   x1 = (x - dx/2 - x_min) / cell_x, x2 = (x + dx/2 - x_min) / cell_x, y1, y2 likewise, c = cos(rz), s = sin(rz),
+ *   theta = [[(x2-x1)/W1 c, -(x2-x1)/W1 s, (x1+x2-W+1)/W1], [(y2-y1)/H1 s, (y2-y1)/H1 c, (y1+y2-H+1)/H1]];
+ * per grid point (row j, column i): u = (2i+1)/G - 1, v = (2j+1)/G - 1, (gx, gy) = theta (u, v, 1), ix = ((gx+1) W - 1)/2,
+ * iy = ((gy+1) H - 1)/2: affine_grid / grid_sample with align_corners=False, bilinear, zeros (what the reference executes; its
+ * theta is written in the W - 1 convention and the quirk is kept). The position is formed in f64, the four weights come from the
+ * unclamped coordinates, a corner outside [0,W) x [0,H) contributes nothing (zero padding, no clamping). Every row is pooled as it
+ * stands: an all-zero padding row samples G*G times at one map point.
+ * -> out (B * R, G*G, C) f32, 16-byte aligned: row (n, j * G + i) holds the C channels of that grid point; the reference's
+ *    (B*R, C, G, G) tensor is out viewed (n, G, G, C) and permuted (0, 3, 1, 2). 16-byte gathers and stores along C, no atomics:
+ *    bit-identical from call to call. No backward (the reference detaches the map and the RoIs). One launch, no synchronisation.
+ * CRB_ERR_ARG: C % 4 != 0, grid_size < 1, a non-positive cell, H or W < 2, roi_row_stride < 7, H*W*C >= 2^31, NULL / misaligned
+ * pointers; CRB_ERR_UNSUPPORTED: grid_size > 16. */
+int crb_roi_bev_pool(const float* bev, int B, int H, int W, int C, const float* rois, int roi_row_stride, int R, int grid_size,
+                     double x_min, double y_min, double cell_x, double cell_y, float* out, void* stream);
 
 /* LLAL loss-prediction module (csrc/loss_net.hip)
  * replaces: LossNet.forward (pcdet/models/roi_heads/loss_net.py:54-70) and its autograd: per shared-FC layer k a Conv1d(C_k -> 1,
