@@ -81,6 +81,48 @@ def second_iou_cfg():
     return c
 
 
+def voxel_rcnn_cfg():
+    """values of tools/cfgs/kitti_models/voxel_rcnn_car.yaml: class Car only, the SECOND trunk with the narrow BEV backbone
+    ([64, 128] filters, [128, 128] up-sampling) + VoxelRCNNHead (6^3 grid, voxel-neighbourhood pooling of x_conv2 / x_conv3 /
+    x_conv4). DATA_CONFIG.DATA_AUGMENTOR carries the model's own queue: gt_sampling Car:15 (no LIMIT_WHOLE_SCENE), flip about x,
+    rotation, scaling; USE_ROAD_PLANE is off for synthetic frames, as in kitti_augmentor_cfg."""
+    c = second_cfg('kitti')
+    c.CLASS_NAMES = ['Car']
+    aug = kitti_augmentor_cfg()
+    aug[0].PREPARE = EasyDict({'filter_by_min_points': ['Car:5'], 'filter_by_difficulty': [-1]})
+    aug[0].SAMPLE_GROUPS = ['Car:15']
+    aug[0].LIMIT_WHOLE_SCENE = False
+    c.DATA_CONFIG = EasyDict({'DATASET': 'KittiDataset', 'DATA_AUGMENTOR': {'DISABLE_AUG_LIST': ['placeholder'], 'AUG_CONFIG_LIST': aug}})
+    m = c.MODEL
+    m.NAME = 'VoxelRCNN'
+    m.BACKBONE_2D = EasyDict(dict(_BEV, NUM_FILTERS=[64, 128], NUM_UPSAMPLE_FILTERS=[128, 128]))
+    m.DENSE_HEAD = EasyDict(_dense_head(KITTI_ANCHORS[:1]))
+    level = lambda radius: {'MLPS': [[32, 32]], 'QUERY_RANGES': [[4, 4, 4]], 'POOL_RADIUS': [radius], 'NSAMPLE': [16],
+                            'POOL_METHOD': 'max_pool'}
+    m.ROI_HEAD = EasyDict({
+        'NAME': 'VoxelRCNNHead', 'CLASS_AGNOSTIC': True, 'SHARED_FC': [256, 256], 'CLS_FC': [256, 256], 'REG_FC': [256, 256],
+        'DP_RATIO': 0.3,
+        'NMS_CONFIG': {
+            'TRAIN': {'NMS_TYPE': 'nms_gpu', 'MULTI_CLASSES_NMS': False, 'NMS_PRE_MAXSIZE': 9000,
+                      'NMS_POST_MAXSIZE': 512, 'NMS_THRESH': 0.8},
+            'TEST': {'NMS_TYPE': 'nms_gpu', 'MULTI_CLASSES_NMS': False, 'USE_FAST_NMS': False, 'SCORE_THRESH': 0.0,
+                     'NMS_PRE_MAXSIZE': 2048, 'NMS_POST_MAXSIZE': 100, 'NMS_THRESH': 0.7}},
+        'ROI_GRID_POOL': {'FEATURES_SOURCE': ['x_conv2', 'x_conv3', 'x_conv4'], 'PRE_MLP': True, 'GRID_SIZE': 6,
+                          'POOL_LAYERS': {'x_conv2': level(0.4), 'x_conv3': level(0.8), 'x_conv4': level(1.6)}},
+        'TARGET_CONFIG': {'BOX_CODER': 'ResidualCoder', 'ROI_PER_IMAGE': 128, 'FG_RATIO': 0.5,
+                          'SAMPLE_ROI_BY_EACH_CLASS': True, 'CLS_SCORE_TYPE': 'roi_iou', 'CLS_FG_THRESH': 0.75,
+                          'CLS_BG_THRESH': 0.25, 'CLS_BG_THRESH_LO': 0.1, 'HARD_BG_RATIO': 0.8, 'REG_FG_THRESH': 0.55},
+        'LOSS_CONFIG': {'CLS_LOSS': 'BinaryCrossEntropy', 'REG_LOSS': 'smooth-l1', 'CORNER_LOSS_REGULARIZATION': True,
+                        'GRID_3D_IOU_LOSS': False,
+                        'LOSS_WEIGHTS': {'rcnn_cls_weight': 1.0, 'rcnn_reg_weight': 1.0, 'rcnn_corner_weight': 1.0,
+                                         'rcnn_iou3d_weight': 1.0, 'code_weights': [1.0, 1.0, 1.0, 1.0, 1.0, 1.0, 1.0]}}})
+    m.POST_PROCESSING.SCORE_THRESH = 0.3
+    m.POST_PROCESSING.NMS_CONFIG.NMS_THRESH = 0.1
+    c.OPTIMIZATION.update({'BATCH_SIZE_PER_GPU': 2, 'LR': 0.01, 'DECAY_STEP_LIST': [35, 45], 'LR_DECAY': 0.1, 'LR_CLIP': 0.0000001,
+                           'LR_WARMUP': False, 'WARMUP_EPOCH': 1})
+    return c
+
+
 def pv_rcnn_cfg(kind='kitti'):
     """values of tools/cfgs/active-kitti_models/pv_rcnn_active_crb.yaml; kind='waymo': the differences of
     tools/cfgs/active-waymo_models/pv_rcnn_active_crb.yaml applied on top (anchors, 4096 keypoints, bev/x_conv3/x_conv4/

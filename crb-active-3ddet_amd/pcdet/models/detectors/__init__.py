@@ -18,6 +18,12 @@ try:
 except ImportError:
     pass
 
+try:
+    from .voxel_rcnn import VoxelRCNN
+    __all__['VoxelRCNN'] = VoxelRCNN
+except ImportError:
+    pass
+
 
 def build_detector(model_cfg, num_class, dataset):
     return __all__[model_cfg.NAME](model_cfg=model_cfg, num_class=num_class, dataset=dataset)

@@ -87,6 +87,17 @@ def get_voxel_centers(voxel_coords, downsample_times, voxel_size, point_cloud_ra
     return (centers + 0.5) * vs + pc_min
 
 
+def generate_voxel2pinds(sparse_tensor):
+    """dense (B, Z, Y, X) int32 tensor holding the feature row of every occupied site, -1 elsewhere (common_utils.py:232-240 with
+    spconv_utils.scatter_point_inds). The definition of the voxel query's lookup and the torch route's index; the HIP route
+    (crbhip.voxel_pool) looks sites up in a hash and never builds it."""
+    ind = sparse_tensor.indices.long()
+    out = torch.full([int(sparse_tensor.batch_size)] + [int(s) for s in sparse_tensor.spatial_shape], -1, dtype=torch.int32,
+                     device=ind.device)
+    out[ind[:, 0], ind[:, 1], ind[:, 2], ind[:, 3]] = torch.arange(ind.shape[0], device=ind.device, dtype=torch.int32)
+    return out
+
+
 _CONSTS = {}
 
 

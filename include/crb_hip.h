@@ -1063,6 +1063,51 @@ int crb_bev_interpolate_backward(const float* dout, int B, int H, int W, int C, 
 int crb_roi_bev_pool(const float* bev, int B, int H, int W, int C, const float* rois, int roi_row_stride, int R, int grid_size,
                      double x_min, double y_min, double cell_x, double cell_y, float* out, void* stream);
 
+/* voxel-neighbourhood RoI grid pooling of Voxel R-CNN (csrc/voxel_pool.hip)
+ * replaces: voxel_query_kernel_stack (pcdet/ops/pointnet2/pointnet2_stack/src/voxel_query_gpu.cu:10-89) with the dense
+ *           (B, Z, Y, X) index of common_utils.generate_voxel2pinds, VoxelQueryAndGrouping (voxel_query_utils.py:51-100) and the
+ *           body of one NeighborVoxelSAModuleMSG scale (voxel_pool_modules.py:96-120: grouping, mlps_pos Conv2d + BatchNorm2d, add,
+ *           ReLU, max / avg pooling over nsample).
+ * crb_voxel_query: xyz (N,3) f32 voxel centres of the level's feature rows, new_xyz (M,3) f32 grid points, new_coords (M,4) i32
+ *   [b, z, y, x] of the grid point AT THE LEVEL (16-byte aligned), shape_dhw / ranges_zyx HOST int32[3], hkeys / hvals / capacity the
+ *   site hash of crb_sparse_hash_build over the level's (N,4) coordinates (any row order; no dense index is ever built).
+ *   Per grid point: scan dz in [-rz, rz], then dy, then dx, ascending; skip sites outside [0,D) x [0,H) x [0,W) and sites without
+ *   a voxel; skip neighbours with dist2 = (px-nx)^2 + (py-ny)^2 + (pz-nz)^2 > radius^2 in f32 (equality is a hit); keep the first
+ *   nsample hits in scan order. -> idx (M, nsample) i32 GLOBAL feature rows, slots behind the last hit filled with the first hit;
+ *   cnt (M) i32 = number of hits kept (0 .. nsample; the scan stops at the nsample-th). cnt == 0: the ball is empty, its idx
+ *   row is all 0 and consumers read row 0 with features and relative xyz zeroed. A frame index outside [0, B) gives an empty ball.
+ *   CRB_ERR_UNSUPPORTED: nsample > 32 or a range > 4.
+ * crb_voxel_pool_moments: sums (9) f64 = {sum dx, dy, dz, sum dx dx, dx dy, dx dz, dy dy, dy dz, dz dz} over ALL M * nsample
+ *   slots, d = xyz[idx] - new_xyz in f32 (fill slots counted again, empty balls count nsample zeros), accumulated in f64 in a fixed
+ *   order (bit-reproducible). mlps_pos is linear in d, so the batch statistics of its BatchNorm2d are w.mu and w^T Sigma w.
+ * crb_voxel_pool_forward: out[m,c] = pool_s relu(features_in[idx[m,s], c] + A[c,0] dx + A[c,1] dy + A[c,2] dz + b[c]), pool = 0
+ *   max / 1 avg over the nsample slots; A (C,3), b (C) = mlps_pos with its BatchNorm2d folded in. An empty ball yields relu(b)
+ *   (the reference's quirk: features and d are zeroed, the bias of the folded BatchNorm is not). features_in (N,C) / out (M,C)
+ *   f32, 16-byte aligned. Nothing of size (M, C, nsample) or (M, 3, nsample) is written in either direction.
+ * crb_voxel_pool_backward: recomputes the values from idx. grad_out (M,C) -> d_Ab (C,4) f32 rows {dA x, dA y, dA z, db} (per-
+ *   workgroup partials in the workspace, reduced in f64 in a fixed order: reproducible) and the gradient of features_in either
+ *   - d_features (N,C) != NULL: ADDED with f32 atomics (the caller zero-fills; the summation order, hence the last bits, vary
+ *     from call to call), or
+ *   - d_features == NULL, max pooling: g_sel (M,C) f32 / a_row (M,C) i32 = the gradient and the feature row it belongs to (-1:
+ *     none), for a deterministic scatter by the caller. Avg pooling: CRB_ERR_UNSUPPORTED.
+ *   Max pooling passes the gradient to the first maximal slot; a maximum of 0 (ReLU inactive) and empty balls pass none.
+ * Supported (crb_voxel_pool_supported, host): C in {32, 64}, 1 <= nsample <= 32; anything else CRB_ERR_UNSUPPORTED. */
+int crb_voxel_pool_supported(int C, int nsample);
+int crb_voxel_query(const float* xyz, int64_t N, const float* new_xyz, const int32_t* new_coords, int64_t M, int B,
+                    const int32_t* shape_dhw, const int32_t* ranges_zyx, float radius, int nsample, const int64_t* hkeys,
+                    const int32_t* hvals, int64_t capacity, int32_t* idx, int32_t* cnt, void* stream);
+int64_t crb_voxel_pool_moments_workspace_bytes(int64_t M);
+int crb_voxel_pool_moments(const float* xyz, const float* new_xyz, const int32_t* idx, const int32_t* cnt, int64_t M, int nsample,
+                           double* sums, void* workspace, int64_t workspace_bytes, void* stream);
+int crb_voxel_pool_forward(const float* features_in, int64_t N, int C, const float* xyz, const float* new_xyz, const int32_t* idx,
+                           const int32_t* cnt, int64_t M, int nsample, int pool, const float* A, const float* b, float* out,
+                           void* stream);
+int64_t crb_voxel_pool_backward_workspace_bytes(int64_t M, int C);
+int crb_voxel_pool_backward(const float* grad_out, const float* features_in, int64_t N, int C, const float* xyz,
+                            const float* new_xyz, const int32_t* idx, const int32_t* cnt, int64_t M, int nsample, int pool,
+                            const float* A, const float* b, float* d_features, float* g_sel, int32_t* a_row, float* d_Ab,
+                            void* workspace, int64_t workspace_bytes, void* stream);
+
 /* LLAL loss-prediction module (csrc/loss_net.hip)
  * replaces: LossNet.forward (pcdet/models/roi_heads/loss_net.py:54-70) and its autograd: per shared-FC layer k a Conv1d(C_k -> 1,
  *           k=1, bias=False) over the R = frames * rows_per_frame RoI rows, BatchNorm1d(1) (train mode: batch statistics over the R
