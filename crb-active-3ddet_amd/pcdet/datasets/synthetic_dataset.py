@@ -23,7 +23,8 @@ class _PointFeatureEncoder(object):
 
 class SyntheticDataset(Dataset):
     def __init__(self, num_frames=64, n_points=20000, kind='kitti', training=True, first_frame=0,
-                 device_voxelize=True, class_names=None):
+                 device_voxelize=True, class_names=None, point_cloud_range=None, voxel_size=None, max_points_per_voxel=None,
+                 max_num_voxels=None):
         assert kind in ('kitti', 'waymo')
         self.kind, self.training = kind, training
         self.n_points, self.first_frame = n_points, first_frame
@@ -41,6 +42,15 @@ class SyntheticDataset(Dataset):
             self.max_num_voxels = {'train': 150000, 'test': 150000}
             nfeat = 5
         self.max_points_per_voxel = 5
+        # another voxel grid over the same frames (PointPillars: pcdet.model_cfgs.pointpillar_dataset_args()); grid_size follows
+        if point_cloud_range is not None:
+            self.point_cloud_range = np.array(point_cloud_range, dtype=np.float32)
+        if voxel_size is not None:
+            self.voxel_size = [float(v) for v in voxel_size]
+        if max_points_per_voxel is not None:
+            self.max_points_per_voxel = int(max_points_per_voxel)
+        if max_num_voxels is not None:
+            self.max_num_voxels = {k: int(v) for k, v in dict(max_num_voxels).items()}
         self.point_feature_encoder = _PointFeatureEncoder(nfeat)
         g = (self.point_cloud_range[3:6] - self.point_cloud_range[0:3]) / np.array(self.voxel_size)
         self.grid_size = np.round(g).astype(np.int64)

@@ -4,9 +4,9 @@ pcdet.config reads the reference's own YAMLs when they are available."""
 from .config import EasyDict
 
 
-def _anchor(cls, size, bottom, matched, unmatched):
+def _anchor(cls, size, bottom, matched, unmatched, stride=8):
     return {'class_name': cls, 'anchor_sizes': [size], 'anchor_rotations': [0, 1.57],
-            'anchor_bottom_heights': [bottom], 'align_center': False, 'feature_map_stride': 8,
+            'anchor_bottom_heights': [bottom], 'align_center': False, 'feature_map_stride': stride,
             'matched_threshold': matched, 'unmatched_threshold': unmatched}
 
 
@@ -121,6 +121,42 @@ def voxel_rcnn_cfg():
     c.OPTIMIZATION.update({'BATCH_SIZE_PER_GPU': 2, 'LR': 0.01, 'DECAY_STEP_LIST': [35, 45], 'LR_DECAY': 0.1, 'LR_CLIP': 0.0000001,
                            'LR_WARMUP': False, 'WARMUP_EPOCH': 1})
     return c
+
+
+def pointpillar_cfg():
+    """values of tools/cfgs/kitti_models/pointpillar.yaml: PillarVFE (one 64-filter PFN layer) on 0.16 x 0.16 x 4 m pillars of at most
+    32 points over [0, -39.68, -3, 69.12, 39.68, 1] (a 432 x 496 x 1 grid, 16,000 / 40,000 pillars), PointPillarScatter, the three-block
+    BEV backbone and the KITTI anchors at feature_map_stride 2. DATA_CONFIG carries the range and the voxel generator's values (what
+    SyntheticDataset(point_cloud_range=, voxel_size=, max_points_per_voxel=, max_num_voxels=) takes) and kitti_augmentor_cfg()'s queue."""
+    c = second_cfg('kitti')
+    c.DATA_CONFIG = EasyDict({
+        'DATASET': 'KittiDataset', 'POINT_CLOUD_RANGE': [0, -39.68, -3, 69.12, 39.68, 1],
+        'DATA_PROCESSOR': [
+            {'NAME': 'mask_points_and_boxes_outside_range', 'REMOVE_OUTSIDE_BOXES': True},
+            {'NAME': 'shuffle_points', 'SHUFFLE_ENABLED': {'train': True, 'test': False}},
+            {'NAME': 'transform_points_to_voxels', 'VOXEL_SIZE': [0.16, 0.16, 4], 'MAX_POINTS_PER_VOXEL': 32,
+             'MAX_NUMBER_OF_VOXELS': {'train': 16000, 'test': 40000}}],
+        'DATA_AUGMENTOR': {'DISABLE_AUG_LIST': ['placeholder'], 'AUG_CONFIG_LIST': kitti_augmentor_cfg()}})
+    m = c.MODEL
+    m.NAME = 'PointPillar'
+    m.VFE = EasyDict({'NAME': 'PillarVFE', 'WITH_DISTANCE': False, 'USE_ABSLOTE_XYZ': True, 'USE_NORM': True, 'NUM_FILTERS': [64]})
+    m.pop('BACKBONE_3D')
+    m.MAP_TO_BEV = EasyDict({'NAME': 'PointPillarScatter', 'NUM_BEV_FEATURES': 64})
+    m.BACKBONE_2D = EasyDict({'NAME': 'BaseBEVBackbone', 'LAYER_NUMS': [3, 5, 5], 'LAYER_STRIDES': [2, 2, 2], 'NUM_FILTERS': [64, 128, 256],
+                              'UPSAMPLE_STRIDES': [1, 2, 4], 'NUM_UPSAMPLE_FILTERS': [128, 128, 128]})
+    m.DENSE_HEAD = EasyDict(_dense_head([_anchor('Car', [3.9, 1.6, 1.56], -1.78, 0.6, 0.45, stride=2),
+                                         _anchor('Pedestrian', [0.8, 0.6, 1.73], -0.6, 0.5, 0.35, stride=2),
+                                         _anchor('Cyclist', [1.76, 0.6, 1.73], -0.6, 0.5, 0.35, stride=2)]))
+    c.OPTIMIZATION.update({'DECAY_STEP_LIST': [35, 45], 'LR_DECAY': 0.1, 'LR_CLIP': 0.0000001, 'LR_WARMUP': False, 'WARMUP_EPOCH': 1})
+    return c
+
+
+def pointpillar_dataset_args(cfg=None):
+    """the keyword arguments that make a SyntheticDataset produce pointpillar_cfg()'s grid"""
+    d = (cfg or pointpillar_cfg()).DATA_CONFIG
+    v = [p for p in d.DATA_PROCESSOR if p['NAME'] == 'transform_points_to_voxels'][0]
+    return {'point_cloud_range': list(d.POINT_CLOUD_RANGE), 'voxel_size': list(v['VOXEL_SIZE']),
+            'max_points_per_voxel': int(v['MAX_POINTS_PER_VOXEL']), 'max_num_voxels': dict(v['MAX_NUMBER_OF_VOXELS'])}
 
 
 def pv_rcnn_cfg(kind='kitti'):

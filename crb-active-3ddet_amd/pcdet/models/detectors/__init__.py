@@ -24,6 +24,9 @@ try:
 except ImportError:
     pass
 
+from .pointpillar import PointPillar
+__all__['PointPillar'] = PointPillar
+
 
 def build_detector(model_cfg, num_class, dataset):
     return __all__[model_cfg.NAME](model_cfg=model_cfg, num_class=num_class, dataset=dataset)

@@ -1108,6 +1108,38 @@ int crb_voxel_pool_backward(const float* grad_out, const float* features_in, int
                             const float* A, const float* b, float* d_features, float* g_sel, int32_t* a_row, float* d_Ab,
                             void* workspace, int64_t workspace_bytes, void* stream);
 
+/* Pillar feature net of PointPillars (csrc/pillar_vfe.hip)
+ * replaces: PillarVFE.forward + PFNLayer.forward (pcdet/models/backbones_3d/vfe/pillar_vfe.py:29-49, 94-123) with one PFN layer:
+ *           the (M, T, K) augmented points, Linear(K -> 64, bias=False), BatchNorm1d(64) on (M, 64, T), ReLU, max over T - three
+ *           (M, T, 64) tensors each way in the reference, none here.
+ * voxels (M, T, C) f32, num_points (M) i32, coords (M, 4) i32 [b, z, y, x] (16-byte aligned), voxel_size (3) / offsets (3) HOST f32
+ * {x, y, z}, offsets = voxel / 2 + range_min. Only the slots t < num_points[m] (clamped to 0 .. T) are read.
+ * Augmented point of a valid slot, K = C + 6: f = [point (C), xyz - mean_xyz, xyz - centre]; mean_xyz = sum over the valid slots
+ * (in f64) / num_points, rounded to f32; centre = (float)coord * voxel + offset in f32, two roundings. Padded slots: f = 0.
+ * crb_pillar_vfe_moments: sums (crb_pillar_vfe_num_moments(C) = (K+1)(K+2)/2 - 1) f64 = the upper triangle of sum g g^T over the valid
+ *   slots, g = [f, 1], rows i = 0 .. K-1 one after the other, row i holding columns j = i .. K (column K: sum f_i). Products and sums
+ *   in f64, per-workgroup partials reduced in a fixed order: bit-reproducible. Two launches.
+ * crb_pillar_vfe_forward: A (Cout, K), b (Cout) -> out (M, Cout) = max over ALL T slots of relu(A f + b); a padded slot has the value
+ *   relu(b) (the reference's quirk: its BatchNorm1d sees the zero rows). One launch, nothing of size (M, T, .) is written.
+ * crb_pillar_vfe_backward: grad_out (M, Cout) -> d_sums (Cout, K + 1) f64: row c = {sum dy f^T (K), sum dy} over the selected slots,
+ *   dy = grad_out where the slot is the first maximal one of its pillar and channel and the maximum is > 0 (a selected padded slot
+ *   adds to sum dy only). f32 inside a workgroup, f64 across workgroups in a fixed order: bit-reproducible. Two launches. There is no
+ *   gradient to the points.
+ * Supported (crb_pillar_vfe_supported, host): C in {4, 5}, 1 <= T <= 32, Cout == 64; anything else CRB_ERR_UNSUPPORTED. */
+int crb_pillar_vfe_supported(int C, int T, int Cout);
+int crb_pillar_vfe_num_moments(int C);
+int64_t crb_pillar_vfe_moments_workspace_bytes(int64_t M, int C);
+int crb_pillar_vfe_moments(const float* voxels, const int32_t* num_points, const int32_t* coords, int64_t M, int T, int C,
+                           const float* voxel_size, const float* offsets, double* sums, void* workspace, int64_t workspace_bytes,
+                           void* stream);
+int crb_pillar_vfe_forward(const float* voxels, const int32_t* num_points, const int32_t* coords, int64_t M, int T, int C,
+                           const float* voxel_size, const float* offsets, const float* A, const float* b, int Cout, float* out,
+                           void* stream);
+int64_t crb_pillar_vfe_backward_workspace_bytes(int64_t M, int C, int Cout);
+int crb_pillar_vfe_backward(const float* grad_out, const float* voxels, const int32_t* num_points, const int32_t* coords, int64_t M,
+                            int T, int C, const float* voxel_size, const float* offsets, const float* A, const float* b, int Cout,
+                            double* d_sums, void* workspace, int64_t workspace_bytes, void* stream);
+
 /* LLAL loss-prediction module (csrc/loss_net.hip)
  * replaces: LossNet.forward (pcdet/models/roi_heads/loss_net.py:54-70) and its autograd: per shared-FC layer k a Conv1d(C_k -> 1,
  *           k=1, bias=False) over the R = frames * rows_per_frame RoI rows, BatchNorm1d(1) (train mode: batch statistics over the R
