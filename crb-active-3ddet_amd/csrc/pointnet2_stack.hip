@@ -1845,8 +1845,13 @@ extern "C" int crb_group_affine_rows_grad_bn_recompute_stack(int B, int64_t M, i
 
 // deterministic form: the per-source-row sums are accumulated in grad_P_fixed (n_src, H) int64, pre-zeroed, as round(value * scale)
 // (integer atomics: the result does not depend on the order in which the slabs arrive); the caller converts back
-// (grad_P = grad_P_fixed / scale). scale is the caller's: 2^40 / (a power of two >= max |grad_z| * max |gamma invstd|) keeps 2^-40 of
-// that magnitude per addend and overflows only beyond 2^22 times it. `part` as above (it never went through atomics).
+// (grad_P = grad_P_fixed / scale). scale is the caller's, a finite f32 > 0 (anything else: CRB_ERR_ARG, nothing is launched). int64
+// wraps silently, so scale * (a bound on |gamma invstd (d - dbeta / n - xhat dgamma / n)|) * (pairs that can hit one row: up to
+// M * nsample) must stay below 2^63; max |grad_z| * max |gamma invstd| is NOT such a bound (the dbeta and xhat dgamma terms).
+// sa_fixed_point_scale of the host mirror (pointnet2_utils.py) derives a power of two that holds for every pair on one row and leaves
+// 62 - ceil(log2(M * nsample)) fractional bits below the bound: 39 at the RoI-grid size (7 M pairs). The conversion of a NaN / Inf
+// value to an integer is a finite number: the caller looks at grad_z (rows of live balls), dbeta and dgamma before it calls (the
+// host mirror returns NaN). `part` as above (it never went through atomics).
 extern "C" int crb_group_affine_rows_grad_bn_recompute_stack_fixed(int B, int64_t M, int H, int nsample, const float* xyz,
                                                                    const int32_t* xyz_batch_cnt, const float* P, const float* new_xyz,
                                                                    const int32_t* new_xyz_batch_cnt, const int32_t* idx,
@@ -1856,7 +1861,7 @@ extern "C" int crb_group_affine_rows_grad_bn_recompute_stack_fixed(int B, int64_
                                                                    const int32_t* sorted_pair, const int32_t* sorted_row, int64_t n_src,
                                                                    int64_t* grad_P_fixed /* pre-zeroed */, float scale, float* part,
                                                                    void* stream) {
-  if (!grad_P_fixed || !(scale > 0.f)) return CRB_ERR_ARG;
+  if (!grad_P_fixed || !(scale > 0.f) || !(scale <= 3.402823466e+38f)) return CRB_ERR_ARG;      // NaN, <= 0, inf
   return group_affine_rows_grad_bn_recompute(B, M, H, nsample, xyz, xyz_batch_cnt, P, new_xyz, new_xyz_batch_cnt, idx, empty_mask, W1x,
                                              grad_z, mean, invstd, gamma, beta, dbeta, dgamma, sorted_pair, sorted_row, n_src, nullptr,
                                              part, stream, grad_P_fixed, scale);

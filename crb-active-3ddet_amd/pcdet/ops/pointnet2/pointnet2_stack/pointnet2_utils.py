@@ -355,6 +355,97 @@ SORTED_SCATTER = __import__('os').environ.get('CRB_SA_SORTED_SCATTER', '1') == '
 SORTED_SCATTER_MIN_PAIRS = 2 * 1024 * 1024
 
 
+FLT_MAX = 3.4028234663852886e38
+# the fixed-point scatter keeps its f32 arithmetic inside [2^-FIXED_PRESCALE_EXP, 2^FIXED_PRESCALE_EXP]: outside it the gradient is
+# moved there by an exact power of two first (sa_first_layer_scatter_fixed)
+FIXED_PRESCALE_EXP = 64
+
+
+def sa_fixed_point_scale(max_gz, max_gi, max_dbeta, max_dgamma, n):
+    """scale of crb_group_affine_rows_grad_bn_recompute_stack_fixed -> (scale, addend_bound). Pure host arithmetic.
+    max_gz = max |grad_z| over the rows of live balls, max_gi = max |gamma invstd|, max_dbeta / max_dgamma = max |dbeta| / |dgamma|
+    over the channels, n = M * nsample pairs (the BatchNorm's row count). All finite and >= 0.
+
+    addend_bound bounds every value the kernel scatters, v = gamma invstd (d - dbeta / n - xhat dgamma / n) with d = grad_z [z > 0]:
+      |d| <= max_gz;  |dbeta / n| <= max_dbeta / n;
+      |xhat| <= sqrt(n) for batch statistics: invstd^2 = 1 / (var + eps) <= n / (y_i - mean)^2 because var = sum_j (y_j - mean)^2 / n
+      contains the term of row i, so |xhat dgamma / n| <= max_dgamma / sqrt(n);
+      |v| <= max_gi (max_gz + max_dbeta / n + max_dgamma / sqrt(n)).
+    It is widened by 2^-8 for the kernel's f32 evaluation (mean, invstd, xhat and the three terms are rounded to f32: a few 2^-24
+    each) and capped at FLT_MAX, the largest finite value an f32 addend can have.
+
+    scale = 2^k with 2^e > addend_bound, L = ceil(log2 n), k = 62 - e - L: every pair may hit one row, and n addends of at most 2^e
+    sum to at most 2^(e + L) = 2^62 / scale - one bit below the int64 sign bit for the n roundings to nearest and the f32 rounding of
+    the up to 64 addends a slab folds before it converts. k is clamped to [-126, 127] (a finite normal f32; clamping only lowers
+    it). What remains below 2^e is 62 - L fractional bits: 39 at the RoI-grid size (7 M pairs, L = 23), 48 at a 16 k-pair layer."""
+    n = int(n)
+    bound = float(max_gi) * (float(max_gz) + float(max_dbeta) / n + float(max_dgamma) / math.sqrt(n))
+    bound = min(bound * (1.0 + 2.0 ** -8), FLT_MAX)
+    e = math.frexp(bound)[1]                                   # bound < 2^e (e = 0 for bound = 0)
+    L = max(n - 1, 0).bit_length()                             # ceil(log2 n)
+    k = min(max(62 - e - L, -126), 127)
+    return 2.0 ** k, bound
+
+
+def _mul_pow2(t, e):
+    """t * 2^e for an f32 tensor, in steps an f32 factor can hold (|e| may pass 127 when t is subnormal); a new tensor"""
+    while e:
+        step = max(min(e, 100), -100)
+        t = t * 2.0 ** step
+        e -= step
+    return t
+
+
+def sa_first_layer_scatter_fixed(B, M, h1, ns, xyz, xc, P, new_xyz, nc, idx, em, w1x, gz1, mean1, invstd1, g1, b1, d1, sp, sr, part):
+    """pass D of SAMlp2TrainConcat.backward in deterministic mode -> grad_P (n_src, h1) f32; `part` (slabs, 3, h1) is written.
+    Float atomics add in arrival order; 64-bit fixed point does not care: the kernel adds round(value * scale) with integer atomics,
+    scale from sa_fixed_point_scale. gz1 (M * ns, h1): rows of empty balls (em) are never read, whatever they hold - pass C does not
+    write them. d1 = (dbeta, dgamma) (2, h1). sp / sr: the pairs in source-row order or None.
+    One read-back: the four maxima the scale needs, as one device tensor. A non-finite entry among them (a live grad_z entry, dbeta,
+    dgamma or gamma invstd that is NaN or Inf: the float path's grad_P then holds NaN / Inf, and an integer cannot) gives an all-NaN
+    grad_P and part. A gradient so small or so large that the f32 arithmetic of the kernel would leave the normal range is first
+    moved to about 1 by a power of two - a copy of gz1, taken on this rare path only: exact (up to entries 2^-126 of the largest), and
+    undone in float64: in the conversion of the result, and in `part`, whose slabs are summed in float64 and returned as ONE slab (the
+    others 0) - a slab that is scaled back into the subnormal range one by one loses half a quantum each. The test is on the bracket
+    G = max |grad_z| + max |dbeta| / n + max |dgamma| / sqrt(n) of the bound (outside 2^-64 .. 2^64), not on max |gamma invstd| * G:
+    gamma and invstd are the layer's own and are left alone, so with a gamma invstd beyond 2^57 the up to 64 addends a slab folds
+    can still pass FLT_MAX before the conversion, as they do in the float path."""
+    dev = gz1.device
+    n = M * ns
+    n_src = P.shape[0]
+    st = cur_stream(dev)
+    live = torch.linalg.vector_norm(gz1.view(M, ns * h1), ord=float('inf'), dim=1)       # max |.| per ball, NaN propagates; one pass
+    live = live.masked_fill(em.view(M).bool(), 0.0)
+    mx = torch.stack([live.max() if M > 0 else live.new_zeros(()), (g1 * invstd1).abs().max(), d1[0].abs().max(), d1[1].abs().max()])
+    max_gz, max_gi, max_db, max_dg = mx.tolist()
+    if not all(math.isfinite(v) for v in (max_gz, max_gi, max_db, max_dg)):
+        part.fill_(float('nan'))
+        return torch.full((n_src, h1), float('nan'), dtype=torch.float32, device=dev)
+    shift = 0
+    nn_ = max(n, 1)
+    G = max_gz + max_db / nn_ + max_dg / math.sqrt(nn_)          # float64: the bracket of the bound above
+    if G > 0.0 and abs(math.frexp(G)[1]) > FIXED_PRESCALE_EXP:
+        shift = -math.frexp(G)[1]
+        gz1, d1 = _mul_pow2(gz1, shift), _mul_pow2(d1, shift)
+        f = 2.0 ** shift
+        max_gz, max_db, max_dg = max_gz * f, max_db * f, max_dg * f
+    scale = sa_fixed_point_scale(max_gz, max_gi, max_db, max_dg, nn_)[0]
+    gP64 = torch.zeros((n_src, h1), dtype=torch.int64, device=dev)
+    check(lib.crb_group_affine_rows_grad_bn_recompute_stack_fixed(B, M, h1, ns, ptr(xyz), ptr(xc), ptr(P), ptr(new_xyz), ptr(nc), ptr(idx),
+                                                                  ptr(em), ptr(w1x), ptr(gz1), ptr(mean1), ptr(invstd1), ptr(g1), ptr(b1),
+                                                                  ptr(d1[0]), ptr(d1[1]), ptr(sp), ptr(sr), n_src, ptr(gP64), scale,
+                                                                  ptr(part), st),
+          'crb_group_affine_rows_grad_bn_recompute_stack_fixed')
+    gP = gP64.double() * (1.0 / scale)
+    if shift:
+        gP = gP * 2.0 ** -shift
+        total = (part.double().sum(0) * 2.0 ** -shift).float()
+        part.zero_()
+        if part.shape[0]:
+            part[0] = total
+    return gP.float()
+
+
 def sa_mlp2_train_supported(h1, h2, nsample):
     return bool(lib.crb_sa_mlp2_train_supported(int(h1), int(h2), int(nsample)))
 
@@ -475,7 +566,6 @@ class SAMlp2TrainConcat(Function):
             # pass D: BatchNorm 1 backward inside the scatter kernel of the first layer. Large layers (the RoI-grid scales) scatter in
             # source-row order: a stable device sort of the pairs, then runs of equal rows are added in LDS and cost one row of
             # atomics per 16-pair segment
-            gP = torch.zeros((feats.shape[0], h1), dtype=torch.float32, device=dev)
             part = torch.empty((int(lib.crb_group_affine_rows_grad_blocks(M, ns)), 3, h1), dtype=torch.float32, device=dev)
             sp = sr = None
             n_src = feats.shape[0]
@@ -487,19 +577,10 @@ class SAMlp2TrainConcat(Function):
                 check(lib.crb_pair_sort_by_source(B, M, ns, ptr(xc), ptr(nc), ptr(idx), ptr(em), n_src, ptr(sp), ptr(sr), ptr(wss), wsb, st),
                       'crb_pair_sort_by_source')
             if torch.are_deterministic_algorithms_enabled():
-                # float atomics add in arrival order; 64-bit fixed point does not care: round(value * 2^40 / R) with R a power of two
-                # >= max |grad| * max |gamma invstd| (2^-40 R per addend, room for sums up to 2^22 R)
-                R = float(gz1.abs().max()) * float((g1c * invstd1).abs().max())
-                scale = 2.0 ** (40 - (math.frexp(R)[1] if R > 0.0 and math.isfinite(R) else 0))
-                gP64 = torch.zeros((feats.shape[0], h1), dtype=torch.int64, device=dev)
-                check(lib.crb_group_affine_rows_grad_bn_recompute_stack_fixed(B, M, h1, ns, ptr(xyz_c), ptr(xc), ptr(P), ptr(new_c), ptr(nc),
-                                                                              ptr(idx), ptr(em), ptr(w1x), ptr(gz1), ptr(mean1),
-                                                                              ptr(invstd1), ptr(g1c), ptr(b1c), ptr(d1[0]), ptr(d1[1]),
-                                                                              ptr(sp), ptr(sr), n_src, ptr(gP64), scale, ptr(part), st),
-                      'crb_group_affine_rows_grad_bn_recompute_stack_fixed')
-                gP = (gP64.double() * (1.0 / scale)).float()
-                del gP64
+                gP = sa_first_layer_scatter_fixed(B, M, h1, ns, xyz_c, xc, P, new_c, nc, idx, em, w1x, gz1, mean1, invstd1, g1c, b1c, d1,
+                                                  sp, sr, part)
             else:
+                gP = torch.zeros((n_src, h1), dtype=torch.float32, device=dev)
                 check(lib.crb_group_affine_rows_grad_bn_recompute_stack(B, M, h1, ns, ptr(xyz_c), ptr(xc), ptr(P), ptr(new_c), ptr(nc),
                                                                         ptr(idx), ptr(em), ptr(w1x), ptr(gz1), ptr(mean1), ptr(invstd1),
                                                                         ptr(g1c), ptr(b1c), ptr(d1[0]), ptr(d1[1]), ptr(sp), ptr(sr), n_src,

@@ -508,8 +508,13 @@ int crb_group_affine_rows_grad_bn_recompute_stack(int B, int64_t M, int H, int n
                                                   float* grad_P, float* part, void* stream);
 /* deterministic form of the call above (torch.use_deterministic_algorithms in the host mirror): what leaves a slab is added into
  * grad_P_fixed (n_src, H) int64, pre-zeroed, as round(value * scale) with 64-bit integer atomics - the sums do not depend on the
- * order in which the slabs arrive; the caller converts back (grad_P = grad_P_fixed / scale). scale > 0: 2^40 / (a power of two >=
- * max |grad_z| * max |gamma * invstd|) keeps 2^-40 of that magnitude per addend and overflows only past 2^22 times it. */
+ * order in which the slabs arrive; the caller converts back (grad_P = grad_P_fixed / scale). scale: a finite f32 > 0, else CRB_ERR_ARG
+ * (NaN, inf, 0 and negative values launch nothing). int64 wraps silently: scale * A * (M * nsample) < 2^63 must hold for a bound A on
+ * the scattered values |gamma invstd (d - dbeta / n - xhat dgamma / n)| - every pair may hit one row. max |grad_z| * max |gamma invstd|
+ * alone is no such bound; A = max |gamma invstd| * (max |grad_z| + max |dbeta| / n + max |dgamma| / sqrt(n)) is one for batch statistics
+ * (|xhat| <= sqrt(n)), maxima over the rows of LIVE balls only (the others are never read and may hold anything). With scale = 2^(62 - e -
+ * ceil(log2 n)), 2^e > A (sa_fixed_point_scale of the host mirror), 62 - ceil(log2 n) fractional bits remain below 2^e: 39 at the
+ * RoI-grid size (7 M pairs). A NaN / Inf value converts to a finite integer: the caller checks grad_z, dbeta and dgamma first. */
 int crb_group_affine_rows_grad_bn_recompute_stack_fixed(int B, int64_t M, int H, int nsample, const float* xyz,
                                                         const int32_t* xyz_batch_cnt, const float* P, const float* new_xyz,
                                                         const int32_t* new_xyz_batch_cnt, const int32_t* idx,
