@@ -151,6 +151,44 @@ def pointpillar_cfg():
     return c
 
 
+def centerpoint_cfg(kind='kitti'):
+    """values of tools/cfgs/waymo_models/centerpoint_without_resnet.yaml: the SECOND trunk + CenterHead (one head for the three
+    classes, 64 shared channels, two-convolution branches, stride-8 targets with at most 500 objects). kind='waymo': the yaml as it
+    stands. kind='kitti': the same model section with the KITTI class names on the KITTI geometry of second_cfg('kitti');
+    POST_CENTER_LIMIT_RANGE is the KITTI point-cloud range."""
+    assert kind in ('kitti', 'waymo')
+    names = ['Car', 'Pedestrian', 'Cyclist'] if kind == 'kitti' else ['Vehicle', 'Pedestrian', 'Cyclist']
+    limit = [0, -40, -3, 70.4, 40, 1] if kind == 'kitti' else [-75.2, -75.2, -2, 75.2, 75.2, 4]
+    return EasyDict({
+        'CLASS_NAMES': names,
+        'DATA_CONFIG': {'DATASET': 'KittiDataset' if kind == 'kitti' else 'WaymoDataset'},
+        'MODEL': {
+            'NAME': 'CenterPoint',
+            'VFE': {'NAME': 'MeanVFE'},
+            'BACKBONE_3D': {'NAME': 'VoxelBackBone8x'},
+            'MAP_TO_BEV': {'NAME': 'HeightCompression', 'NUM_BEV_FEATURES': 256},
+            'BACKBONE_2D': dict(_BEV),
+            'DENSE_HEAD': {
+                'NAME': 'CenterHead', 'CLASS_AGNOSTIC': False, 'CLASS_NAMES_EACH_HEAD': [list(names)],
+                'SHARED_CONV_CHANNEL': 64, 'USE_BIAS_BEFORE_NORM': True, 'NUM_HM_CONV': 2,
+                'SEPARATE_HEAD_CFG': {
+                    'HEAD_ORDER': ['center', 'center_z', 'dim', 'rot'],
+                    'HEAD_DICT': {'center': {'out_channels': 2, 'num_conv': 2}, 'center_z': {'out_channels': 1, 'num_conv': 2},
+                                  'dim': {'out_channels': 3, 'num_conv': 2}, 'rot': {'out_channels': 2, 'num_conv': 2}}},
+                'TARGET_ASSIGNER_CONFIG': {'FEATURE_MAP_STRIDE': 8, 'NUM_MAX_OBJS': 500, 'GAUSSIAN_OVERLAP': 0.1, 'MIN_RADIUS': 2},
+                'LOSS_CONFIG': {'LOSS_WEIGHTS': {'cls_weight': 1.0, 'loc_weight': 2.0,
+                                                 'code_weights': [1.0, 1.0, 1.0, 1.0, 1.0, 1.0, 1.0, 1.0]}},
+                'POST_PROCESSING': {'SCORE_THRESH': 0.1, 'POST_CENTER_LIMIT_RANGE': limit, 'MAX_OBJ_PER_SAMPLE': 500,
+                                    'NMS_CONFIG': {'NMS_TYPE': 'nms_gpu', 'NMS_THRESH': 0.7, 'NMS_PRE_MAXSIZE': 4096,
+                                                   'NMS_POST_MAXSIZE': 500}}},
+            'POST_PROCESSING': {'RECALL_THRESH_LIST': [0.3, 0.5, 0.7], 'EVAL_METRIC': 'kitti' if kind == 'kitti' else 'waymo'},
+        },
+        'OPTIMIZATION': {'BATCH_SIZE_PER_GPU': 4, 'NUM_EPOCHS': 30, 'OPTIMIZER': 'adam_onecycle', 'LR': 0.003, 'WEIGHT_DECAY': 0.01,
+                         'MOMENTUM': 0.9, 'MOMS': [0.95, 0.85], 'PCT_START': 0.4, 'DIV_FACTOR': 10, 'DECAY_STEP_LIST': [35, 45],
+                         'LR_DECAY': 0.1, 'LR_CLIP': 0.0000001, 'LR_WARMUP': False, 'WARMUP_EPOCH': 1, 'GRAD_NORM_CLIP': 10},
+    })
+
+
 def pointpillar_dataset_args(cfg=None):
     """the keyword arguments that make a SyntheticDataset produce pointpillar_cfg()'s grid"""
     d = (cfg or pointpillar_cfg()).DATA_CONFIG

@@ -27,6 +27,9 @@ except ImportError:
 from .pointpillar import PointPillar
 __all__['PointPillar'] = PointPillar
 
+from .centerpoint import CenterPoint
+__all__['CenterPoint'] = CenterPoint
+
 
 def build_detector(model_cfg, num_class, dataset):
     return __all__[model_cfg.NAME](model_cfg=model_cfg, num_class=num_class, dataset=dataset)

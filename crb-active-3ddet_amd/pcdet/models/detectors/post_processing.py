@@ -164,7 +164,10 @@ GT_STAT_FIELDS = 5          # num_bbox, n_counted, mean, median, variance per cl
 
 
 def class_names_of(model):
-    return [c['class_name'] for c in model.model_cfg.DENSE_HEAD.ANCHOR_GENERATOR_CONFIG]
+    anchors = getattr(model.model_cfg.DENSE_HEAD, 'ANCHOR_GENERATOR_CONFIG', None)
+    if anchors is None:                                    # anchor-free dense head (CenterHead): the detector's own class list
+        return list(model.class_names)
+    return [c['class_name'] for c in anchors]
 
 
 def frame_offsets_of(batch_dict):

@@ -1187,6 +1187,73 @@ int crb_lossnet_forward(const CrbLossNetArgs* args, const float* lin_w, const fl
 int crb_lossnet_backward(const CrbLossNetArgs* args, const float* lin_w, const float* d_out, void* ws, int64_t ws_bytes,
                          const CrbLossNetGrads* grads, void* stream);
 
+/* Anchor-free centre head of CenterPoint (csrc/center_head.hip)
+ * replaces: CenterHead.assign_targets + assign_target_of_single_head (pcdet/models/dense_heads/center_head.py:103-219) with
+ *           centernet_utils.gaussian_radius / gaussian2D / draw_gaussian_to_heatmap (pcdet/models/model_utils/centernet_utils.py:9-69):
+ *           three nested Python loops over heads, frames and boxes on the host, one .item() and one numpy window per box;
+ *           CenterHead.get_loss (:225-251) with FocalLossCenterNet / RegLossCenterNet (pcdet/utils/loss_utils.py:264-386): ~25 launches
+ *           per head and an .item() per term; decode_bbox_from_heatmap (centernet_utils.py:154-216) behind its top-K.
+ * Maps are (B, C, H, W) f32 addressed as b * C*H*W + c * stride_c + (y * W + x) * stride_p: {H*W, 1} is NCHW memory, {1, C} is
+ * channels_last memory; the maps are read (and their gradients written) where the convolutions left them.
+ *
+ * crb_center_assign_targets: gt_boxes (B, M, box_dim) f32, box_dim = 7 + E + 1, class (1 .. num_class, anything else: no object) in
+ *   the last column. class_head / class_local (num_class) HOST i32: the head that names class c + 1 (-1: none) and its index there.
+ *   head_channels (num_heads) HOST i32. Outputs, all zeroed inside the sequence: heatmaps = the heads' (B, C_h, H, W) NCHW blocks one
+ *   after the other; target_boxes (num_heads, B, NMAX, 8 + E) f32; inds (num_heads, B, NMAX) i64 = y * W + x; masks (num_heads, B,
+ *   NMAX) i64. The slot of a box is its rank among the frame's boxes of the same head in input order; ranks >= NMAX are dropped; a
+ *   box with dx <= 0 or dy <= 0 keeps its slot, which stays zero. Centre, radius and the copied columns in f32 as the reference
+ *   rounds them (gaussian_overlap is a double: its derived constants 1 - o, 1 + o, ... are formed in f64 and rounded to f32 once, as
+ *   torch rounds a Python scalar); log / cos / sin and the Gaussian in f64, rounded once. Overlaps combine by an integer atomicMax on the bit pattern
+ *   of the non-negative values: bit-reproducible. Two launches (slots, draw) and five memsets. Limits: num_class <= 16, num_heads <= 8,
+ *   E <= 8 (else CRB_ERR_UNSUPPORTED).
+ * crb_center_loss_forward (one head): hm logits + heatmap -> loss (2) f64 = {hm_loss * cls_weight, loc_loss * loc_weight},
+ *   stats (2) f64 = {num_pos, sum of masks} for the backward. Sigmoid clamped to [1e-4, 1 - 1e-4]; num_pos over the whole batch;
+ *   num_pos == 0: -neg_loss undivided. Regression: masked L1 of the maps of `reg` (HEAD_ORDER) gathered at inds against
+ *   target_boxes, per-column sums / max(sum mask, 1), times code_weights. Terms and sums in f64, per-workgroup partials added in a
+ *   fixed order: bit-reproducible. Two launches.
+ * crb_center_loss_backward: grad_loss (2) f32 -> d_hm (layout of hm; zero outside the clamp range) and d_reg maps (layout of
+ *   the reg maps: zero-filled, (+/-) code_weight * loc_weight / num at the inds cells, objects of one cell counted in integers
+ *   before the product). One launch, no atomics on floats.
+ *   NMAX <= 4096, else CRB_ERR_UNSUPPORTED from the forward AND the backward (the Python route takes the torch route there).
+ * crb_center_decode (one head): top_val / top_idx (B, K) = logits and flat indices picked from the (C * H * W) logits of a frame
+ *   (idx_channels_last = 0: c * H*W + cell, 1: cell * C + c) -> boxes (B, K, 7 + vel channels) = {x, y, z, exp(dim), atan2(sin, cos),
+ *   vel}, scores (B, K) = sigmoid, labels (B, K) i64 (class in head), keep (B, K) u8 = inside limit_range (6, HOST) on x, y, z and
+ *   score > score_thresh. `reg` holds center, center_z, dim, rot (+ vel) in this order. One launch.
+ * ---------------------------------------------------------------------------------------------- */
+#define CRB_CENTER_MAX_MAPS 8
+#define CRB_CENTER_MAX_CODE 16
+typedef struct CrbCenterMaps {
+  const float* ptr[CRB_CENTER_MAX_MAPS];      /* (B, channels[i], H, W) */
+  float* grad[CRB_CENTER_MAX_MAPS];           /* backward only: same layout as ptr[i] */
+  int64_t stride_c[CRB_CENTER_MAX_MAPS];
+  int64_t stride_p[CRB_CENTER_MAX_MAPS];
+  int32_t channels[CRB_CENTER_MAX_MAPS];
+  int32_t num_maps;
+} CrbCenterMaps;
+typedef struct CrbCenterLossCfg {
+  float code_weights[CRB_CENTER_MAX_CODE];
+  float cls_weight, loc_weight;
+} CrbCenterLossCfg;
+int64_t crb_center_assign_workspace_bytes(int num_heads, int B, int num_max_objs);
+int crb_center_assign_targets(const float* gt_boxes, int B, int M, int box_dim, int num_class, const int32_t* class_head,
+                              const int32_t* class_local, int num_heads, const int32_t* head_channels, int H, int W,
+                              const float* pc_range_xy, const float* voxel_size_xy, int feature_map_stride, int num_max_objs,
+                              double gaussian_overlap, int min_radius, float* heatmaps, float* target_boxes, int64_t* inds,
+                              int64_t* masks, void* workspace, int64_t workspace_bytes, void* stream);
+int64_t crb_center_loss_workspace_bytes(int B, int H, int W);
+int crb_center_loss_forward(const float* hm, int64_t hm_stride_c, int64_t hm_stride_p, const float* heatmap, int B, int C, int H, int W,
+                            const CrbCenterMaps* reg, const float* target_boxes, const int64_t* inds, const int64_t* masks,
+                            int num_max_objs, const CrbCenterLossCfg* cfg, double* loss, double* stats, void* workspace,
+                            int64_t workspace_bytes, void* stream);
+int crb_center_loss_backward(const float* hm, int64_t hm_stride_c, int64_t hm_stride_p, const float* heatmap, int B, int C, int H, int W,
+                             const CrbCenterMaps* reg, const float* target_boxes, const int64_t* inds, const int64_t* masks,
+                             int num_max_objs, const CrbCenterLossCfg* cfg, const double* stats, const float* grad_loss, float* d_hm,
+                             void* stream);
+int crb_center_decode(const float* top_val, const int64_t* top_idx, int B, int K, int C, int H, int W, int idx_channels_last,
+                      const CrbCenterMaps* reg, const float* pc_range_xy, const float* voxel_size_xy, int feature_map_stride,
+                      const float* limit_range, float score_thresh, float* boxes, float* scores, int64_t* labels, uint8_t* keep,
+                      void* stream);
+
 #ifdef __cplusplus
 }
 #endif
