@@ -189,6 +189,36 @@ def centerpoint_cfg(kind='kitti'):
     })
 
 
+def centerpoint_dyn_pillar_cfg():
+    """values of tools/cfgs/waymo_models/centerpoint_dyn_pillar_1x.yaml: DynPillarVFE (two PFN layers, dynamic voxelization: no cap on
+    points per pillar or on pillars) on 0.32 x 0.32 x 6 m pillars over [-74.88, -74.88, -2, 74.88, 74.88, 4] (a 468 x 468 x 1 grid),
+    PointPillarScatter, the three-block BEV backbone with a stride-1 first block and CenterHead at FEATURE_MAP_STRIDE 1."""
+    c = centerpoint_cfg('waymo')
+    c.DATA_CONFIG = EasyDict({
+        'DATASET': 'WaymoDataset', 'POINT_CLOUD_RANGE': [-74.88, -74.88, -2, 74.88, 74.88, 4.0],
+        'DATA_PROCESSOR': [
+            {'NAME': 'mask_points_and_boxes_outside_range', 'REMOVE_OUTSIDE_BOXES': True},
+            {'NAME': 'shuffle_points', 'SHUFFLE_ENABLED': {'train': True, 'test': True}},
+            {'NAME': 'transform_points_to_voxels_placeholder', 'VOXEL_SIZE': [0.32, 0.32, 6.0]}]})
+    m = c.MODEL
+    m.VFE = EasyDict({'NAME': 'DynPillarVFE', 'WITH_DISTANCE': False, 'USE_ABSLOTE_XYZ': True, 'USE_NORM': True, 'NUM_FILTERS': [64, 64]})
+    m.pop('BACKBONE_3D')
+    m.MAP_TO_BEV = EasyDict({'NAME': 'PointPillarScatter', 'NUM_BEV_FEATURES': 64})
+    m.BACKBONE_2D = EasyDict({'NAME': 'BaseBEVBackbone', 'LAYER_NUMS': [3, 5, 5], 'LAYER_STRIDES': [1, 2, 2], 'NUM_FILTERS': [64, 128, 256],
+                              'UPSAMPLE_STRIDES': [1, 2, 4], 'NUM_UPSAMPLE_FILTERS': [128, 128, 128]})
+    m.DENSE_HEAD.TARGET_ASSIGNER_CONFIG.FEATURE_MAP_STRIDE = 1
+    m.DENSE_HEAD.POST_PROCESSING.POST_CENTER_LIMIT_RANGE = [-80, -80, -10.0, 80, 80, 10.0]
+    c.OPTIMIZATION.BATCH_SIZE_PER_GPU = 2
+    return c
+
+
+def centerpoint_dyn_pillar_dataset_args(cfg=None):
+    """the keyword arguments that make a SyntheticDataset produce centerpoint_dyn_pillar_cfg()'s grid (Waymo-like frames, 5 features)"""
+    d = (cfg or centerpoint_dyn_pillar_cfg()).DATA_CONFIG
+    v = [p for p in d.DATA_PROCESSOR if p['NAME'] == 'transform_points_to_voxels_placeholder'][0]
+    return {'kind': 'waymo', 'point_cloud_range': list(d.POINT_CLOUD_RANGE), 'voxel_size': list(v['VOXEL_SIZE'])}
+
+
 def pointpillar_dataset_args(cfg=None):
     """the keyword arguments that make a SyntheticDataset produce pointpillar_cfg()'s grid"""
     d = (cfg or pointpillar_cfg()).DATA_CONFIG

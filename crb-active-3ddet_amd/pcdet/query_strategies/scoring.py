@@ -31,8 +31,12 @@ class RecordLayout:
     @classmethod
     def for_model(cls, model):
         cfg = model.model_cfg
-        nc = len(cfg.DENSE_HEAD.ANCHOR_GENERATOR_CONFIG)
-        nms = cfg.POST_PROCESSING.NMS_CONFIG
+        if cfg.DENSE_HEAD.get('ANCHOR_GENERATOR_CONFIG', None) is None:     # anchor-free centre head: its own classes and NMS settings
+            nc = sum(len(h) for h in cfg.DENSE_HEAD.CLASS_NAMES_EACH_HEAD)
+            nms = cfg.DENSE_HEAD.POST_PROCESSING.NMS_CONFIG
+        else:
+            nc = len(cfg.DENSE_HEAD.ANCHOR_GENERATOR_CONFIG)
+            nms = cfg.POST_PROCESSING.NMS_CONFIG
         post = min(int(nms.NMS_POST_MAXSIZE), int(nms.NMS_PRE_MAXSIZE))
         roi = cfg.get('ROI_HEAD', None)
         if roi is not None:

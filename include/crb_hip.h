@@ -1254,6 +1254,96 @@ int crb_center_decode(const float* top_val, const int64_t* top_idx, int B, int K
                       const float* limit_range, float score_thresh, float* boxes, float* scores, int64_t* labels, uint8_t* keep,
                       void* stream);
 
+/* Dynamic voxelization and the segmented mean (csrc/dyn_voxelize.hip)
+ * replaces: the grouping of DynamicPillarVFE.forward (pcdet/models/backbones_3d/vfe/dynamic_pillar_vfe.py:93-103, 132-138) and
+ *           DynamicMeanVFE.forward (dynamic_mean_vfe.py:53-72): floor / mask / merge_coords / torch.unique(return_inverse) /
+ *           torch_scatter.scatter_mean. Every point in range belongs to its voxel: no cap on points per voxel, none on voxels.
+ * points (n_points, row_stride) f32 rows [b, x, y, z, ...]; frames need not be contiguous. b = (int)column 0, truncated as .int()
+ * does; rows with b outside 0 .. B - 1 are dropped. Cell c = floorf(__fdiv_rn(__fsub_rn(p, min), voxel)) per axis in f32 (torch's
+ * arithmetic); a point is kept iff 0 <= c < grid on every masked axis. A NaN in b, x, y or z drops the point in both modes.
+ *   CRB_DYN_PILLAR: x and y masked (z is NOT, as in the reference), key = (b * gx + cx) * gy + cy,            coords = [b, 0, cy, cx]
+ *   CRB_DYN_VOXEL:  x, y and z masked,                              key = ((b * gx + cx) * gy + cy) * gz + cz, coords = [b, cz, cy, cx]
+ * Keys are 64-bit. range_min_xyz / voxel_size_xyz (3) HOST f32, grid_xyz (3) HOST i32 (each < 2^24).
+ * Outputs: counts (2) i32 = {M voxels, Nk kept points}; perm (n_points) i32: its first Nk entries are the kept point rows, voxel by
+ * voxel in ascending key order (torch.unique's order), input order inside a voxel (a stable radix sort over the bits of the key
+ * range only); seg_offsets (max_voxels + 1) i32: voxel v owns perm[seg_offsets[v] .. seg_offsets[v + 1]), seg_offsets[M] = Nk;
+ * coords (max_voxels, 4) i32, rows 0 .. M - 1 written. max_voxels >= min(n_points, B * cells per frame), else CRB_ERR_ARG.
+ * n_points == 0: counts and seg_offsets[0] are zeroed, nothing is launched. No atomics: bit-reproducible.
+ * crb_dyn_mean_vfe: out (M, C) f32 = mean over the voxel's points of columns 1 .. C of `points`: an f64 sum in segment order,
+ *   divided in f64, rounded once. M == 0: nothing is launched. One launch.
+ * crb_dyn_canonical_order: perm_out (n_kept) i32 = perm with the points of every voxel re-ordered by content: ascending in the bit
+ *   patterns (as unsigned) of feature columns 1 .. C, column 1 most significant; rows of equal content keep their order. A sum in
+ *   segment order over perm_out depends on the multiset of input rows only, not on their order. perm_out != perm. C stable 32-bit
+ *   radix sorts and one over the bits of M; workspace crb_dyn_canonical_order_workspace_bytes(n_kept). n_kept == 0: no launch. */
+#define CRB_DYN_PILLAR 0
+#define CRB_DYN_VOXEL 1
+int64_t crb_dyn_voxelize_workspace_bytes(int64_t n_points);
+int crb_dyn_voxelize(const float* points, int64_t n_points, int row_stride, int B, int mode, const float* range_min_xyz,
+                     const float* voxel_size_xyz, const int32_t* grid_xyz, int64_t max_voxels, int32_t* perm, int32_t* seg_offsets,
+                     int32_t* coords, int32_t* counts, void* workspace, int64_t workspace_bytes, void* stream);
+int crb_dyn_mean_vfe(const float* points, int64_t n_points, int row_stride, int C, const int32_t* perm, const int32_t* seg_offsets,
+                     int64_t M, float* out, void* stream);
+int64_t crb_dyn_canonical_order_workspace_bytes(int64_t n_kept);
+int crb_dyn_canonical_order(const float* points, int64_t n_points, int row_stride, int C, const int32_t* perm, int64_t n_kept,
+                            const int32_t* seg_offsets, int64_t M, int32_t* perm_out, void* workspace, int64_t workspace_bytes,
+                            void* stream);
+
+/* Two-layer pillar feature net of DynamicPillarVFE over variable-length segments (csrc/dyn_pillar_vfe.hip)
+ * replaces: PFNLayerV2.forward x 2 and the feature augmentation of DynamicPillarVFE.forward (pcdet/models/backbones_3d/vfe/
+ *           dynamic_pillar_vfe.py:35-46, 105-124) with NUM_FILTERS [64, 64]: six or seven (N, 64) f32 tensors kept for the backward
+ *           pass in the reference, nothing of size (N, .) here but the sorted point order.
+ * Segments: perm / seg_offsets / coords of crb_dyn_voxelize in CRB_DYN_PILLAR mode, perm passed through crb_dyn_canonical_order
+ * where the results must not depend on the order of the input rows (all sums run in segment order); pillar_mean (M, C) of crb_dyn_mean_vfe (columns
+ * 0 .. 2 are read). Augmented point, K = C + 6: f = [point (C), xyz - pillar mean, x - ((float)cx * vx + ox), y - ((float)cy * vy +
+ * oy), z - oz]; voxel_xy (2) / offsets (3) HOST f32, offsets = voxel / 2 + range_min.
+ * Layer 1: x1 = relu(A1 f + b1), A1 (32, K), b1 (32) the folded affine; x_max (32) = its maximum over the pillar. Layer 2: y =
+ * W2 [x1; x_max], W2 (64, 64) the raw weight; v = scale2 y + shift2; out = max over the pillar of relu(v).
+ * crb_dyn_pillar_moments: sums (crb_dyn_pillar_num_moments(C)) f64, the layout of crb_pillar_vfe_moments, over all kept points.
+ * crb_dyn_pillar_stats2: sums (128) f64 = {sum y (64), sum y^2 (64)} over all kept points.
+ * crb_dyn_pillar_forward: out (M, 64). One launch; a pillar is walked twice.
+ * crb_dyn_pillar_backward_a: arg2 (M, 64) i32 = position in its segment of the first maximal point of v per pillar and channel, -1
+ *   where the maximum is <= 0; sums (128) f64 = {sum dy2, sum dy2 yhat2}, dy2 = grad_out at the selected points, yhat2 = (y - mean2)
+ *   inv_sigma2.
+ * crb_dyn_pillar_backward_b: d_sums (64 * 64 + 32 * 12) f64 = dW2 (64, 64) = sum dx2 [x1; x_max]^T with dx2 = scale2 (dy2 - k1 -
+ *   yhat2 k2) over ALL points, then rows j = 0 .. 31 of 12: {G1[j] = sum dy1 f^T (K), G0[j] = sum dy1 at column K, zeros}, dy1 = the
+ *   gradient at the layer-1 BatchNorm output (own W2^T dx2 half, plus the pillar sum of the x_max half at the first maximal point of
+ *   the channel, ReLU mask applied). k1 = sum dy2 / n, k2 = dgamma2 / n in training, zeros in eval mode.
+ * Sums: f32 inside a workgroup at most, f64 across workgroups in a fixed order, no atomics: bit-reproducible. workspace:
+ * crb_dyn_pillar_workspace_bytes(M) for every call. Supported (crb_dyn_pillar_vfe_supported, host): C in {4, 5}, two layers of 64
+ * filters; anything else CRB_ERR_UNSUPPORTED. M >= 1. There is no gradient to the points. */
+typedef struct CrbDynPillarArgs {
+  const float* points;          /* (n_points, row_stride) rows [b, x, y, z, ...] */
+  const int32_t* perm;          /* (Nk) */
+  const int32_t* seg_offsets;   /* (M + 1) */
+  const int32_t* coords;        /* (M, 4) [b, 0, cy, cx] */
+  const float* pillar_mean;     /* (M, C) */
+  const float* A1;              /* (32, K) */
+  const float* b1;              /* (32) */
+  const float* W2;              /* (64, 64) */
+  const float* scale2;          /* (64) */
+  const float* shift2;          /* (64) */
+  const float* mean2;           /* (64) backward */
+  const float* inv_sigma2;      /* (64) backward */
+  const float* k1;              /* (64) backward_b */
+  const float* k2;              /* (64) backward_b */
+  int64_t n_points;
+  int64_t M;
+  int32_t row_stride;
+  int32_t C;
+  float voxel_xy[2];
+  float offsets[3];
+} CrbDynPillarArgs;
+int crb_dyn_pillar_vfe_supported(int C, int num_layers, int filters0, int filters1);
+int crb_dyn_pillar_num_moments(int C);
+int64_t crb_dyn_pillar_workspace_bytes(int64_t M);
+int crb_dyn_pillar_moments(const CrbDynPillarArgs* args, double* sums, void* workspace, int64_t workspace_bytes, void* stream);
+int crb_dyn_pillar_stats2(const CrbDynPillarArgs* args, double* sums, void* workspace, int64_t workspace_bytes, void* stream);
+int crb_dyn_pillar_forward(const CrbDynPillarArgs* args, float* out, void* stream);
+int crb_dyn_pillar_backward_a(const CrbDynPillarArgs* args, const float* grad_out, int32_t* arg2, double* sums, void* workspace,
+                              int64_t workspace_bytes, void* stream);
+int crb_dyn_pillar_backward_b(const CrbDynPillarArgs* args, const float* grad_out, const int32_t* arg2, double* d_sums, void* workspace,
+                              int64_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
