@@ -311,6 +311,30 @@ def pv_rcnn_cfg(kind='kitti'):
     })
 
 
+def pv_rcnn_plusplus_cfg(kind='kitti'):
+    """pv_rcnn_cfg(kind) with the PFE section and the RoI-head NMS sizes of tools/cfgs/waymo_models/pv_rcnn_plusplus.yaml: keypoints by
+    sectorized proposal-centric sampling (SPC, 6 sectors, 1.6 m around the proposals), feature sources bev / x_conv3 / x_conv4 /
+    raw_points with their neighbours filtered by the RoIs (2.4 / 4.0 / 6.4 m), 90 fused features, 100 test RoIs. The set-abstraction
+    layers and the RoI grid pool stay PV-RCNN's StackSAModuleMSG: the yaml's VectorPoolAggregationModuleMSG is not ported."""
+    c = pv_rcnn_cfg(kind)
+    m = c.MODEL
+    m.NAME = 'PVRCNNPlusPlus'
+    m.PFE.SAMPLE_METHOD = 'SPC'
+    m.PFE.SPC_SAMPLING = EasyDict({'NUM_SECTORS': 6, 'SAMPLE_RADIUS_WITH_ROI': 1.6})
+    m.PFE.NUM_OUTPUT_FEATURES = 90
+    m.PFE.FEATURES_SOURCE = ['bev', 'x_conv3', 'x_conv4', 'raw_points']
+    for src, radius in (('raw_points', 2.4), ('x_conv3', 4.0), ('x_conv4', 6.4)):
+        m.PFE.SA_LAYER[src].update({'FILTER_NEIGHBOR_WITH_ROI': True, 'RADIUS_OF_NEIGHBOR_WITH_ROI': radius})
+    for src in ('x_conv1', 'x_conv2'):
+        m.PFE.SA_LAYER.pop(src)
+    m.ROI_HEAD.pop('SAMPLING_ROUND', None)
+    m.ROI_HEAD.NMS_CONFIG.TRAIN.update({'NMS_PRE_MAXSIZE': 9000, 'NMS_POST_MAXSIZE': 512, 'NMS_THRESH': 0.8})
+    m.ROI_HEAD.NMS_CONFIG.TEST.update({'NMS_PRE_MAXSIZE': 1024, 'NMS_POST_MAXSIZE': 100, 'NMS_THRESH': 0.7, 'SCORE_THRESH': 0.1})
+    c.ACTIVE_TRAIN.METHOD = 'random'
+    c.ACTIVE_TRAIN.pop('ACTIVE_CONFIG', None)
+    return c
+
+
 def pv_rcnn_llal_cfg():
     """values of tools/cfgs/active-kitti_models/pv_rcnn_active_llal.yaml: the KITTI PV-RCNN with the LLAL loss-prediction module
     (ROI_HEAD.LOSS_NET), no MC-dropout rounds, the loss net frozen during detector training (OPTIMIZATION.LOSS_NET_SKIP) and

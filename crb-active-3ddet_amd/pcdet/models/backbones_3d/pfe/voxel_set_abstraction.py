@@ -4,6 +4,9 @@ bilinear BEV feature lookup, multi-scale set abstraction over raw points and the
 Host-side differences from the reference: the per-frame Python loops (FPS per frame :250-256, bs_mask loops :346-347,
 :176-204) are replaced by batched calls — all frames share ONE FPS launch when they have the same point count, and the
 per-frame counts come from one bincount instead of `(idx == k).sum()` round trips."""
+import math
+
+import numpy as np
 import torch
 import torch.nn as nn
 
@@ -27,6 +30,122 @@ def bilinear_interpolate_torch(im, x, y):
     wc = (x - x0.type_as(x)) * (y1.type_as(y) - y)
     wd = (x - x0.type_as(x)) * (y - y0.type_as(y))
     return (im[y0, x0] * wa[:, None] + im[y1, x0] * wb[:, None] + im[y0, x1] * wc[:, None] + im[y1, x1] * wd[:, None])
+
+
+# ---- SPC: sectorized proposal-centric keypoint sampling (voxel_set_abstraction.py:45-121 of the reference) ----------------------
+# Two routes give the same keypoints. The device route (crbhip/spc.py, csrc/spc_sampling.hip) takes all frames through four
+# launches and one read-back. The torch route is the reference's expressions as torch ops: it runs on host tensors too, and is the
+# yardstick of the device route (tests/test_spc_gpu.py). SPC_DEVICE_ROUTE = False sends device tensors through the torch route.
+SPC_DEVICE_ROUTE = True
+
+
+def _spc_on_device(t):
+    return SPC_DEVICE_ROUTE and t.is_cuda
+
+
+def roi_mask_torch(rois, points, sample_radius_with_roi, num_max_points_of_part=200000):
+    """the reference's expression (its chunks of num_max_points_of_part only bound the (N, R) tensor and change no value)"""
+    masks = []
+    for s in range(0, max(points.shape[0], 1), max(int(num_max_points_of_part), 1)):
+        distance = (points[s:s + num_max_points_of_part, None, :] - rois[None, :, 0:3]).norm(dim=-1)
+        min_dis, min_dis_roi_idx = distance.min(dim=-1)
+        roi_max_dim = (rois[min_dis_roi_idx, 3:6] / 2).norm(dim=-1)
+        masks.append(min_dis < roi_max_dim + sample_radius_with_roi)
+    return torch.cat(masks, dim=0)
+
+
+def sample_points_with_roi(rois, points, sample_radius_with_roi, num_max_points_of_part=200000):
+    """rois (M, 7 + C), points (N, 3) of one frame -> (sampled_points (N_out, 3), point_mask (N)). A zero-padded RoI row takes
+    part like any other (centre at the origin, size 0), and a frame of which nothing is kept keeps its first point: both as in
+    the reference. num_max_points_of_part is accepted for the signature; the device route forms no (N, R) tensor to chunk."""
+    if _spc_on_device(points) and points.shape[0] > 0:
+        from crbhip import spc
+        pts = points.detach().float().contiguous()
+        off = torch.tensor([0, pts.shape[0]], dtype=torch.int32, device=pts.device)
+        point_mask = spc.roi_proximity_mask(pts, 0, off, rois.detach().float()[None], sample_radius_with_roi)
+    else:
+        point_mask = roi_mask_torch(rois, points, sample_radius_with_roi, num_max_points_of_part)
+    sampled_points = points[:1] if point_mask.sum() == 0 else points[point_mask, :]
+    return sampled_points, point_mask
+
+
+def sector_quota(cur_num_points, num_points, num_sampled_points):
+    """min(n_k, ceil((n_k / N) * K)) with exactly the reference's three f64 operations (ratio * K is not the exact rational)"""
+    ratio = cur_num_points / num_points
+    return min(cur_num_points, math.ceil(ratio * num_sampled_points))
+
+
+def _brev10(k):
+    r = torch.zeros_like(k)
+    for b in range(10):
+        r = r | (((k >> b) & 1) << (9 - b))
+    return r
+
+
+def stack_fps_torch(xyz, xyz_batch_cnt, num_sampled_points):
+    """the reference's stack_farthest_point_sampling_kernel as torch ops on any device -> (sum m) int64 GLOBAL indices. Per
+    segment: first pick = first point, running distances from 1e10, d = (dx * dx + dy * dy) + dz * dz in f32, and its fixed
+    1024-thread strided scan + LDS tree as a total order: larger distance, then smaller bit-reversed (k mod 1024), then smaller k."""
+    out, s = [], 0
+    for n, m in zip(xyz_batch_cnt, num_sampled_points):
+        n, m = int(n), min(int(m), int(n))
+        p = xyz[s:s + n]
+        k = torch.arange(n, device=xyz.device)
+        rank = _brev10(k & 1023) * (1 << 32) + k
+        temp = torch.full((n,), 1e10, dtype=torch.float32, device=xyz.device)
+        old = torch.zeros((), dtype=torch.int64, device=xyz.device)
+        picks = [old] if m > 0 else []
+        for _ in range(1, m):
+            q = p[old]
+            dx, dy, dz = p[:, 0] - q[0], p[:, 1] - q[1], p[:, 2] - q[2]
+            temp = torch.minimum(dx * dx + dy * dy + dz * dz, temp)
+            old = torch.argmin(torch.where(temp == temp.max(), rank, torch.full_like(rank, 1 << 62)))
+            picks.append(old)
+        if picks:
+            out.append(torch.stack(picks) + s)
+        s += n
+    return torch.cat(out) if out else torch.zeros((0,), dtype=torch.int64, device=xyz.device)
+
+
+def sector_fps_torch(points, num_sampled_points, num_sectors):
+    """the reference's sector_fps, line by line; returns (sampled_points, xyz_batch_cnt, num_sampled_points_list).
+    A point whose sector index reaches num_sectors (azimuth exactly pi) belongs to no sector: the loop runs k < num_sectors.
+    Deviation: when that leaves no sector at all, the one segment of all points samples min(n, K) - the reference asks its
+    kernel for K unclamped and reads out of range when K > n."""
+    sector_size = np.pi * 2 / num_sectors
+    point_angles = torch.atan2(points[:, 1], points[:, 0]) + np.pi
+    sector_idx = (point_angles / sector_size).floor().clamp(min=0, max=num_sectors)
+    xyz_points_list, xyz_batch_cnt, num_sampled_points_list = [], [], []
+    for k in range(num_sectors):
+        mask = (sector_idx == k)
+        cur_num_points = mask.sum().item()
+        if cur_num_points > 0:
+            xyz_points_list.append(points[mask])
+            xyz_batch_cnt.append(cur_num_points)
+            num_sampled_points_list.append(sector_quota(cur_num_points, points.shape[0], num_sampled_points))
+    if len(xyz_batch_cnt) == 0:
+        xyz_points_list.append(points)
+        xyz_batch_cnt.append(len(points))
+        num_sampled_points_list.append(min(len(points), num_sampled_points))
+    xyz = torch.cat(xyz_points_list, dim=0)
+    sampled_pt_idxs = stack_fps_torch(xyz.contiguous(), xyz_batch_cnt, num_sampled_points_list)
+    return xyz[sampled_pt_idxs], xyz_batch_cnt, num_sampled_points_list
+
+
+def sector_fps(points, num_sampled_points, num_sectors):
+    """points (N, 3) of one frame -> sampled_points (N_out, 3): FPS inside each of num_sectors azimuth sectors for the sector's
+    share of num_sampled_points; sectors ascending, picks in pick order. No points: no keypoints (the reference fails there)."""
+    if points.shape[0] == 0:
+        return points[:0]
+    if _spc_on_device(points):
+        from crbhip import spc
+        pts = points.detach().float().contiguous()
+        off = torch.tensor([0, pts.shape[0]], dtype=torch.int32, device=pts.device)
+        plan = spc.spc_plan(pts, 0, off, torch.ones((pts.shape[0],), dtype=torch.bool, device=pts.device), num_sectors, num_sampled_points)
+        _, kp = spc.fps_segments(plan['xyz'], plan['seg'], plan['header'][0:1], int(num_sampled_points) + int(num_sectors),
+                                 want_idx=False, want_keypoints=True)
+        return kp[:int(plan['header'][2].cpu()), 1:4]
+    return sector_fps_torch(points, num_sampled_points, num_sectors)[0]
 
 
 BEV_INTERP_KERNEL = True   # crb_bev_interpolate_forward / _backward (one launch each) instead of the torch expression below
@@ -136,8 +255,41 @@ class VoxelSetAbstraction(nn.Module):
         return (im[r0, x0c] * wa[:, None] + im[r1, x0c] * wb[:, None] + im[r0, x1c] * wc[:, None] +
                 im[r1, x1c] * wd[:, None])
 
+    def sectorized_proposal_centric_sampling(self, roi_boxes, points):
+        """roi_boxes (M, 7 + C), points (N, 3) of one frame -> sampled_points (N_out, 3)  (voxel_set_abstraction.py:206-225)"""
+        cfg = self.model_cfg.SPC_SAMPLING
+        if points.shape[0] == 0:
+            return points[:0]
+        sampled_points, _ = sample_points_with_roi(rois=roi_boxes, points=points, sample_radius_with_roi=cfg.SAMPLE_RADIUS_WITH_ROI,
+                                                   num_max_points_of_part=cfg.get('NUM_POINTS_OF_EACH_SAMPLE_PART', 200000))
+        return sector_fps(points=sampled_points, num_sampled_points=self.model_cfg.NUM_KEYPOINTS, num_sectors=cfg.NUM_SECTORS)
+
+    def _spc_sampled_points(self, batch_dict, src_points, batch_indices):
+        """SAMPLE_METHOD SPC -> keypoints (sum M_b, 4): frames in order, sectors ascending inside a frame, picks in pick order
+        inside a sector. Device tensors: all frames through crbhip.spc.spc_sample (one read-back); else frame by frame through
+        the torch route."""
+        batch_size, cfg = batch_dict['batch_size'], self.model_cfg.SPC_SAMPLING
+        rois = batch_dict['rois']
+        if _spc_on_device(src_points):
+            from crbhip import spc
+            if self.model_cfg.POINT_SOURCE == 'raw_points' and batch_dict['points'].dtype == torch.float32:
+                pts, col, bs = batch_dict['points'].detach().contiguous(), 1, batch_dict['points'][:, 0]
+            else:
+                pts, col, bs = src_points.detach().float().contiguous(), 0, batch_indices.to(torch.int32)
+            off = spc.frame_offsets(_batch_counts(bs, batch_size))
+            keypoints, counts = spc.spc_sample(pts, col, off, rois.detach().float(), cfg.SAMPLE_RADIUS_WITH_ROI, cfg.NUM_SECTORS,
+                                               self.model_cfg.NUM_KEYPOINTS)
+            batch_dict['point_coords_counts_host'] = counts        # (the frames' own keypoint counts: the point head pads by them)
+            return keypoints
+        kps = []
+        for b in range(batch_size):
+            cur = self.sectorized_proposal_centric_sampling(roi_boxes=rois[b], points=src_points[batch_indices == b])
+            kps.append(torch.cat((cur.new_ones(cur.shape[0], 1) * b, cur), dim=1))
+        batch_dict['point_coords_counts_host'] = [int(k.shape[0]) for k in kps]
+        return torch.cat(kps, dim=0)
+
     def get_sampled_points(self, batch_dict):
-        """-> keypoints (B*K, 4) [bs_idx, x, y, z]  (voxel_set_abstraction.py:224-275, SAMPLE_METHOD FPS)"""
+        """-> keypoints [bs_idx, x, y, z]: (B*K, 4) for SAMPLE_METHOD FPS, (sum M_b, 4) for SPC (voxel_set_abstraction.py:224-281)"""
         batch_size = batch_dict['batch_size']
         K = self.model_cfg.NUM_KEYPOINTS
         if self.model_cfg.POINT_SOURCE == 'raw_points':
@@ -150,8 +302,11 @@ class VoxelSetAbstraction(nn.Module):
             batch_indices = batch_dict['voxel_coords'][:, 0].long()
         else:
             raise NotImplementedError
+        batch_dict.pop('point_coords_counts_host', None)
+        if self.model_cfg.SAMPLE_METHOD == 'SPC':
+            return self._spc_sampled_points(batch_dict, src_points, batch_indices)
         if self.model_cfg.SAMPLE_METHOD != 'FPS':
-            raise NotImplementedError('SPC sampling is PV-RCNN++ only (out of scope)')
+            raise NotImplementedError(self.model_cfg.SAMPLE_METHOD)
         counts = batch_dict.get('point_frame_counts_host', None)
         if counts is None:
             counts = torch.bincount(batch_indices, minlength=batch_size).tolist()
@@ -176,7 +331,24 @@ class VoxelSetAbstraction(nn.Module):
 
     @staticmethod
     def aggregate_keypoint_features_from_one_source(batch_size, aggregate_func, xyz, xyz_features, xyz_bs_idxs, new_xyz,
-                                                    new_xyz_batch_cnt, **unused):
+                                                    new_xyz_batch_cnt, filter_neighbors_with_roi=False, radius_of_neighbor=None,
+                                                    num_max_points_of_part=200000, rois=None):
+        """filter_neighbors_with_roi (FILTER_NEIGHBOR_WITH_ROI of the source): only the rows of xyz / xyz_features within
+        radius_of_neighbor of their nearest RoI (sample_points_with_roi's mask, without its keep-the-first-point rule) are
+        handed to the aggregation, in input order; the gradient reaches the kept feature rows. rois (B, R, 7 + C)."""
+        if filter_neighbors_with_roi:
+            if _spc_on_device(xyz):
+                from crbhip import spc
+                pts = xyz.detach().float().contiguous()
+                off = spc.frame_offsets(_batch_counts(xyz_bs_idxs, batch_size))
+                valid = spc.roi_proximity_mask(pts, 0, off, rois.detach().float(), radius_of_neighbor)
+            else:
+                valid = torch.zeros((xyz.shape[0],), dtype=torch.bool, device=xyz.device)
+                for b in range(batch_size):
+                    bs_mask = xyz_bs_idxs == b
+                    valid[bs_mask] = roi_mask_torch(rois[b], xyz[bs_mask], radius_of_neighbor, num_max_points_of_part)
+            keep = torch.nonzero(valid).view(-1)             # (ascending rows: the stable compaction; sizes the filtered tensors)
+            xyz, xyz_features, xyz_bs_idxs = xyz[keep], xyz_features[keep], xyz_bs_idxs[keep]
         xyz_batch_cnt = _batch_counts(xyz_bs_idxs, batch_size)
         _, pooled = aggregate_func(xyz=xyz.contiguous(), xyz_batch_cnt=xyz_batch_cnt, new_xyz=new_xyz,
                                    new_xyz_batch_cnt=new_xyz_batch_cnt, features=xyz_features.contiguous())
@@ -191,6 +363,8 @@ class VoxelSetAbstraction(nn.Module):
         this before its module loop; forward() joins the stream."""
         pts = batch_dict.get('points', None)
         if not self.PREFETCH_KEYPOINTS or pts is None or not pts.is_cuda or self.model_cfg.POINT_SOURCE != 'raw_points':
+            return
+        if self.model_cfg.get('SAMPLE_METHOD', 'FPS') == 'SPC':      # the sampling needs the first stage's rois: nothing to start early
             return
         main = torch.cuda.current_stream(pts.device)
         side = getattr(self, '_kp_stream', None)
@@ -218,6 +392,14 @@ class VoxelSetAbstraction(nn.Module):
         pts.record_stream(side)
         batch_dict['_keypoints_prefetched'] = (kp, done)
 
+    def _roi_filter_args(self, src_name, batch_dict):
+        """FILTER_NEIGHBOR_WITH_ROI / RADIUS_OF_NEIGHBOR_WITH_ROI of one SA source as arguments of
+        aggregate_keypoint_features_from_one_source; a source without the flag passes nothing"""
+        cfg = self.model_cfg.SA_LAYER[src_name]
+        if not cfg.get('FILTER_NEIGHBOR_WITH_ROI', False):
+            return {}
+        return {'filter_neighbors_with_roi': True, 'radius_of_neighbor': cfg['RADIUS_OF_NEIGHBOR_WITH_ROI'], 'rois': batch_dict['rois']}
+
     def forward(self, batch_dict):
         pre = batch_dict.pop('_keypoints_prefetched', None)
         if pre is not None:
@@ -233,8 +415,9 @@ class VoxelSetAbstraction(nn.Module):
             feats.append(self.interpolate_from_bev_features(keypoints, batch_dict['spatial_features'], batch_size,
                                                             bev_stride=batch_dict['spatial_features_stride']))
         new_xyz = keypoints[:, 1:4].contiguous()
-        # (get_sampled_points returns exactly NUM_KEYPOINTS rows per frame, frames in order; any other keypoint source is counted)
-        if keypoints.shape[0] == batch_size * self.model_cfg.NUM_KEYPOINTS:
+        # (FPS returns exactly NUM_KEYPOINTS rows per frame, frames in order; SPC and any other keypoint source are counted: an SPC
+        # total can equal B * NUM_KEYPOINTS with unequal frames)
+        if self.model_cfg.get('SAMPLE_METHOD', 'FPS') == 'FPS' and keypoints.shape[0] == batch_size * self.model_cfg.NUM_KEYPOINTS:
             new_xyz_batch_cnt = torch.full((batch_size,), self.model_cfg.NUM_KEYPOINTS, dtype=torch.int32, device=keypoints.device)
         else:
             new_xyz_batch_cnt = _batch_counts(keypoints[:, 0], batch_size)
@@ -243,7 +426,7 @@ class VoxelSetAbstraction(nn.Module):
             feats.append(self.aggregate_keypoint_features_from_one_source(
                 batch_size=batch_size, aggregate_func=self.SA_rawpoints, xyz=raw[:, 1:4],
                 xyz_features=raw[:, 4:].contiguous(), xyz_bs_idxs=raw[:, 0], new_xyz=new_xyz,
-                new_xyz_batch_cnt=new_xyz_batch_cnt))
+                new_xyz_batch_cnt=new_xyz_batch_cnt, **self._roi_filter_args('raw_points', batch_dict)))
         for k, src_name in enumerate(self.SA_layer_names):
             sp = batch_dict['multi_scale_3d_features'][src_name]
             xyz = common_utils.get_voxel_centers(sp.indices[:, 1:4], downsample_times=self.downsample_times_map[src_name],
@@ -251,7 +434,7 @@ class VoxelSetAbstraction(nn.Module):
             feats.append(self.aggregate_keypoint_features_from_one_source(
                 batch_size=batch_size, aggregate_func=self.SA_layers[k], xyz=xyz.contiguous(),
                 xyz_features=sp.features.contiguous(), xyz_bs_idxs=sp.indices[:, 0], new_xyz=new_xyz,
-                new_xyz_batch_cnt=new_xyz_batch_cnt))
+                new_xyz_batch_cnt=new_xyz_batch_cnt, **self._roi_filter_args(src_name, batch_dict)))
         point_features = torch.cat(feats, dim=-1)
         batch_dict['point_features_before_fusion'] = point_features.view(-1, point_features.shape[-1])
         batch_dict['point_features'] = fc_rows(self.vsa_point_feature_fusion, point_features.view(-1, point_features.shape[-1]))

@@ -19,7 +19,8 @@ class PointHeadSimple(PointHeadTemplate):
                                          extra_width=self.model_cfg.TARGET_CONFIG.GT_EXTRA_WIDTH).view(B, -1,
                                                                                                         gt_boxes.shape[-1])
         return self.assign_stack_targets(points=input_dict['point_coords'], gt_boxes=gt_boxes, extend_gt_boxes=extend,
-                                         set_ignore_flag=True, use_ball_constraint=False, ret_part_labels=False)
+                                         set_ignore_flag=True, use_ball_constraint=False, ret_part_labels=False,
+                                         point_counts=input_dict.get('point_coords_counts_host', None))
 
     def get_loss(self, tb_dict=None, reduce=True):
         tb_dict = {} if tb_dict is None else tb_dict

@@ -94,13 +94,29 @@ class PointHeadTemplate(nn.Module):
         return nn.Sequential(*layers)
 
     def assign_stack_targets(self, points, gt_boxes, extend_gt_boxes=None, ret_box_labels=False, ret_part_labels=False,
-                             set_ignore_flag=True, use_ball_constraint=False, central_radius=2.0):
-        """points (N,4) [b,x,y,z], frame-sorted, the same count per frame; gt_boxes (B,M,8)
+                             set_ignore_flag=True, use_ball_constraint=False, central_radius=2.0, point_counts=None):
+        """points (N,4) [b,x,y,z], frame-sorted, the same count per frame unless point_counts (B host ints: the frames' own counts,
+        SPC keypoints) says otherwise; gt_boxes (B,M,8)
         -> point_cls_labels (N) long: class (or 1) inside a gt box, -1 in the enlarged shell only, 0 elsewhere"""
         assert points.dim() == 2 and points.shape[1] == 4 and gt_boxes.dim() == 3 and gt_boxes.shape[2] == 8
         assert set_ignore_flag and not use_ball_constraint and not ret_box_labels and not ret_part_labels, \
             'only the PointHeadSimple target mode is on the hot path'
         B = gt_boxes.shape[0]
+        if point_counts is not None and len(set(int(c) for c in point_counts)) > 1:
+            # ragged frames: the dense (B, max, 3) form of the same points (pad rows far outside every box), labels gathered back
+            cnt = [int(c) for c in point_counts]
+            assert len(cnt) == B and sum(cnt) == points.shape[0], (cnt, tuple(points.shape))
+            M = max(cnt)
+            start = torch.tensor([sum(cnt[:b]) for b in range(B)], device=points.device)
+            frame = torch.repeat_interleave(torch.arange(B, device=points.device), torch.tensor(cnt, device=points.device),
+                                            output_size=points.shape[0])
+            flat = frame * M + (torch.arange(points.shape[0], device=points.device) - start[frame])
+            dense = points.new_full((B * M, 4), 1e6)
+            dense[:, 0] = torch.arange(B, device=points.device).repeat_interleave(M)
+            dense[flat] = points
+            padded = self.assign_stack_targets(dense, gt_boxes, extend_gt_boxes, ret_box_labels, ret_part_labels, set_ignore_flag,
+                                               use_ball_constraint, central_radius)
+            return {'point_cls_labels': padded['point_cls_labels'][flat], 'point_box_labels': None, 'point_part_labels': None}
         bs = points[:, 0].long()
         M = int(points.shape[0] // B)
         if points.shape[0] != M * B:

@@ -24,6 +24,9 @@ try:
 except ImportError:
     pass
 
+from .pv_rcnn_plusplus import PVRCNNPlusPlus
+__all__['PVRCNNPlusPlus'] = PVRCNNPlusPlus
+
 from .pointpillar import PointPillar
 __all__['PointPillar'] = PointPillar
 

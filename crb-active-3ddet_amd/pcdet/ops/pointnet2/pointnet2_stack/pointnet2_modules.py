@@ -37,7 +37,8 @@ FUSED_TRAIN = __import__('os').environ.get('CRB_SA_TRAIN_FUSED', '1') == '1'
 def build_local_aggregation_module(input_channels, config):
     name = config.get('NAME', 'StackSAModuleMSG')
     if name != 'StackSAModuleMSG':
-        raise NotImplementedError(name + ' (VectorPool is PV-RCNN++ only: out of scope, SURVEY §2.1 row 4)')
+        raise NotImplementedError(name + ' needs the vector_pool / three_nn_for_vector_pool ops, which this port does not have yet '
+                                         '(PV-RCNN++ runs with StackSAModuleMSG layers: pcdet.model_cfgs.pv_rcnn_plusplus_cfg)')
     mlps = [[input_channels] + list(m) for m in config.MLPS]
     layer = StackSAModuleMSG(radii=config.POOL_RADIUS, nsamples=config.NSAMPLE, mlps=mlps, use_xyz=True,
                              pool_method='max_pool')

@@ -1344,6 +1344,36 @@ int crb_dyn_pillar_backward_a(const CrbDynPillarArgs* args, const float* grad_ou
 int crb_dyn_pillar_backward_b(const CrbDynPillarArgs* args, const float* grad_out, const int32_t* arg2, double* d_sums, void* workspace,
                               int64_t workspace_bytes, void* stream);
 
+/* Sectorized proposal-centric keypoint sampling (csrc/spc_sampling.hip)
+ * replaces: sample_points_with_roi and sector_fps (pcdet/models/backbones_3d/pfe/voxel_set_abstraction.py:45-121) with the per-frame
+ *           loop of get_sampled_points (:250-274), and stack_farthest_point_sampling_kernel (pointnet2_stack/src/sampling_gpu.cu).
+ * All frames of a batch share every launch; nothing is read back between the three calls.
+ * `points`: the address of the x column of row 0 of an f32 matrix with `row_stride` floats per row (x, y, z adjacent); rows are
+ * stacked frame by frame, frame b = rows frame_offsets[b] .. frame_offsets[b + 1] (device i32, B + 1 ascending entries).
+ * crb_roi_proximity_mask: rois (B, R, roi_stride >= 6) [x, y, z, dx, dy, dz, ...], zero rows included like any other. Per point
+ *   mask = min_r |p - c_r| < |dims_nearest / 2| + radius (f32; nearest = the lowest r of the minimum), nearest (n) i32 or NULL.
+ *   R == 0: nothing is kept.
+ * crb_spc_plan: mask (n) u8 as above. sector (n) u8 = floor((atan2f(y, x) + pi) * inv_sector_size) clamped to [0, S] for EVERY point
+ *   (inv_sector_size = 1.f / (float)(2 pi / S)); a frame with points but none kept keeps its first point; kept points of sector S
+ *   belong to no segment unless all kept points of the frame do (then they are the frame's one segment, m = min(n, K)). Segments are
+ *   ordered by (frame, sector); segment j = seg_table[8 j ..] = {first row of xyz_out, n, m, first output row, frame, 0, 0, 0} with
+ *   m = min(n, ceil(((double)n / (double)kept_in_frame) * (double)K)); xyz_out (n, 3) / src_idx (n): the segments' points in input
+ *   order and their rows in `points`; seg_table holds B * S rows; header (3 + B) i32 = {segments, rows of xyz_out, keypoints,
+ *   keypoints of frame 0 .. B - 1}. B * (S + 1) <= 4096, S <= 254.
+ * crb_fps_segments: one 1024-thread workgroup per table row (rows past *num_segments, a device i32 or NULL, do nothing; rows that
+ *   point outside `rows` / `out_capacity` are skipped). First pick = the segment's first point, running distances start at 1e10,
+ *   ties as the reference's 1024-thread scan + tree. out_idx (out_capacity) rows of xyz, out_keypoints (out_capacity, 4)
+ *   [frame, x, y, z]; either may be NULL. temp (rows) f32 is needed when rows > 20480 (a segment may be that long:
+ *   up to 20480 points a segment keeps coordinates and distances in registers, beyond that the distances live in temp). */
+int crb_roi_proximity_mask(const float* points, int64_t n, int row_stride, const int32_t* frame_offsets, int B, const float* rois, int R,
+                           int roi_stride, float radius, uint8_t* mask, int32_t* nearest, void* stream);
+int64_t crb_spc_plan_workspace_bytes(int B, int S);
+int crb_spc_plan(const float* points, int64_t n, int row_stride, const int32_t* frame_offsets, int B, const uint8_t* mask, int S, int K,
+                 float inv_sector_size, uint8_t* sector, float* xyz_out, int32_t* src_idx, int32_t* seg_table, int32_t* header,
+                 void* workspace, int64_t workspace_bytes, void* stream);
+int crb_fps_segments(const float* xyz, int64_t rows, const int32_t* seg_table, const int32_t* num_segments, int max_segments,
+                     int64_t out_capacity, float* temp, int32_t* out_idx, float* out_keypoints, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
