@@ -331,30 +331,50 @@ class _BNReLUConcatTrain(torch.autograd.Function):
             col += C
         ctx.save_for_backward(*saved)
         ctx.relu, ctx.widths = int(relu), widths
+        ctx.set_materialize_grads(False)          # no gradient arrives when the head computes this backward itself (crbhip.head_bn)
+        global _CONCAT_SAVED
+        _CONCAT_SAVED = saved
         return out
 
     @staticmethod
     def backward(ctx, dz):
-        import ctypes
+        if dz is None:                            # the map's only consumer returned no gradient for it: nothing to launch
+            return (None,) * (1 + 7 * len(ctx.widths))
         dz = dz.contiguous().float()
-        n, total = dz.shape
         saved = ctx.saved_tensors
         grads, col = [None], 0
         for i, C in enumerate(ctx.widths):
             x, mean, invstd, g, b = saved[5 * i:5 * i + 5]
-            dev = x.device
-            dx = torch.empty_like(x)
-            dgamma = torch.empty((C,), dtype=torch.float32, device=dev)
-            dbeta = torch.empty_like(dgamma)
-            wsb = lib.crb_bn_workspace_bytes(n, C)
-            ws, tk = _scratch(dev, wsb)
-            dzp = ctypes.c_void_p(dz.data_ptr() + 4 * col)
-            _bn_check(lib.crb_bn_relu_backward(ptr(x), dzp, total, n, C, ptr(mean), ptr(invstd), ptr(g), ptr(b), ctx.relu,
-                                           ptr(dx), ptr(dgamma), ptr(dbeta), ptr(ws), wsb, ptr(tk), cur_stream(dev)),
-                  'crb_bn_relu_backward')
+            dx, dgamma, dbeta = concat_backward(x, dz, col, mean, invstd, g, b, ctx.relu)
             grads += [dx, dgamma, dbeta, None, None, None, None]
             col += C
         return tuple(grads)
+
+
+_CONCAT_SAVED = None       # what the last _BNReLUConcatTrain.forward saved, for the record bn_relu_concat notes on the map
+
+
+def concat_backward(x, dz, col, mean, invstd, g, b, relu=1, want_dx=True):
+    """training BatchNorm(+ReLU) backward of one branch x (n, C) whose gradient is the columns [col, col + C) of the row-major dz:
+    -> (dx or None, dgamma, dbeta) (crb_bn_relu_backward; dx = NULL computes the reduced gradients only)"""
+    import ctypes
+    n, C = x.shape
+    dev = x.device
+    dx = torch.empty_like(x) if want_dx else None
+    dgamma = torch.empty((C,), dtype=torch.float32, device=dev)
+    dbeta = torch.empty_like(dgamma)
+    wsb = lib.crb_bn_workspace_bytes(n, C)
+    ws, tk = _scratch(dev, wsb)
+    dzp = ctypes.c_void_p(dz.data_ptr() + 4 * col)
+    _bn_check(lib.crb_bn_relu_backward(ptr(x), dzp, dz.shape[1], n, C, ptr(mean), ptr(invstd), ptr(g), ptr(b), int(relu), ptr(dx),
+                                       ptr(dgamma), ptr(dbeta), ptr(ws), wsb, ptr(tk), cur_stream(dev)), 'crb_bn_relu_backward')
+    return dx, dgamma, dbeta
+
+
+def concat_reduce(x, dz, col, mean, invstd, g, b, relu=1):
+    """(dbeta, dgamma) of one branch: the reduce pass of `concat_backward` alone"""
+    _, dgamma, dbeta = concat_backward(x, dz, col, mean, invstd, g, b, relu, want_dx=False)
+    return dbeta, dgamma
 
 
 def bn_relu_concat(xs, bns, relu=True):
@@ -377,7 +397,15 @@ def bn_relu_concat(xs, bns, relu=True):
         with torch.no_grad():
             bn.num_batches_tracked += 1
         args += [x, bn.weight, bn.bias, bn.eps, bn.running_mean, bn.running_var, float(bn.momentum)]
-    return _BNReLUConcatTrain.apply(relu, *args)
+    global _CONCAT_SAVED
+    out = _BNReLUConcatTrain.apply(relu, *args)
+    saved, _CONCAT_SAVED = _CONCAT_SAVED, None
+    if torch.is_grad_enabled() and saved is not None:
+        # what a linear head on this map needs to run this backward itself (crbhip.head_bn; travels with the tensor like _crb_bn_slabs)
+        from . import head_bn
+        out._crb_head_bn = head_bn.Record(out, [(x, bn.weight, bn.bias) for x, bn in zip(xs, bns)],
+                                          [tuple(saved[5 * i:5 * i + 5]) for i in range(len(xs))], relu)
+    return out
 
 
 class _BNReLUMaxConcatTrain(torch.autograd.Function):

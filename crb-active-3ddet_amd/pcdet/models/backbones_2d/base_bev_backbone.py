@@ -298,6 +298,8 @@ class BaseBEVBackbone(nn.Module):
             rows = [p.permute(0, 2, 3, 1).reshape(n * h * w_, p.shape[1]) for p in pre]
             cat = bnrelu.bn_relu_concat(rows, [d[1] for d in self.deblocks[:len(pre)]], relu=True)
             ups = [cat.view(n, h, w_, cat.shape[1]).permute(0, 3, 1, 2)]
+            if len(self.deblocks) == len(self.blocks) and getattr(cat, '_crb_head_bn', None) is not None:
+                ups[0]._crb_head_bn = cat._crb_head_bn         # for a linear head on this map (crbhip.head_bn)
         elif fuse_cat:
             ups = [d[2](d[1](p)) for d, p in zip(self.deblocks, pre)]
         x = torch.cat(ups, dim=1) if len(ups) > 1 else ups[0]

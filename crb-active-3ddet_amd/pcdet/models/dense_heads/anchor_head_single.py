@@ -47,7 +47,16 @@ class AnchorHeadSingle(AnchorHeadTemplate):
                 # channels_last: the 1x1 convolution is the GEMM (B*H*W, 512) x (512, sum C); its output rows already are the
                 # (B,H,W,sum C) layout the reference permutes to
                 n, _, h, w_ = feats.shape
-                y = LinearRows.apply(rows, w.flatten(1), b).view(n, h, w_, w.shape[0])
+                y = None
+                record = getattr(feats, '_crb_head_bn', None)
+                if record is not None:
+                    # the map is the concatenated BatchNorm + ReLU output of the backbone: the head's backward and that BatchNorm's
+                    # run as one pair of streaming launches, the map's gradient is never formed and the map is not kept
+                    from crbhip import head_bn
+                    y = head_bn.linear(rows, w.flatten(1), b, record)
+                if y is None:
+                    y = LinearRows.apply(rows, w.flatten(1), b)
+                y = y.view(n, h, w_, w.shape[0])
             else:
                 y = torch.nn.functional.conv2d(feats, w, b).permute(0, 2, 3, 1)            # (B,H,W,sum C)
             outs = torch.split(y, [h.out_channels for h in heads], dim=3)

@@ -1023,6 +1023,33 @@ int64_t crb_rows_gemm4_wgrad_workspace_bytes(int cin, int cout, int stride);
 int crb_rows_gemm4_wgrad(const float* x, const float* dy, float* dw, int64_t s_ci, int64_t s_co, int64_t s_a, int64_t s_b, int N,
                          int H, int W, int cin, int cout, int stride, void* workspace, int64_t workspace_bytes, void* stream);
 
+/* Backward of BatchNorm(train) -> ReLU -> concat -> linear head (csrc/head_bn.hip): the head out = z W^T + b reads the concatenated
+ * map z (n, Ct) = relu(gamma xhat + beta) of `nbranch` branch inputs x_i (n, width) (base_bev_backbone.py:100-104 followed by
+ * anchor_head_single.py:57-72 as one convolution). With dOut (n, K) contiguous, W (K, Ct) contiguous, mask = [gamma xhat + beta > 0]:
+ *   P2[k][c] = sum_r dOut[r][k] mask[r][c],  P3[k][c] = sum_r dOut[r][k] mask[r][c] xhat[r][c]
+ *   dbeta = sum_k W P2, dgamma = sum_k W P3, dW = gamma P3 + beta P2, dx = gamma invstd (mask (dOut . W) - dbeta / n - xhat dgamma / n)
+ * so the gradient of the map is never formed and the map is not read. Products on the bf16 matrix pipe through the exact three-way
+ * split (Inf -> NaN); no atomics: bit-reproducible. Nothing is read past row n or past k = K.
+ * par (4, Ct) f32: mean | invstd | gamma | beta of the concatenated channels.
+ * crb_head_bn_supported: nbranch == 2, width in {128, 256}, K in {60, 72}; anything else CRB_ERR_UNSUPPORTED from every call.
+ * crb_head_bn_sums: -> sums (crb_head_bn_sums_count f64) = P2 (K, Ct) | P3 (K, Ct) | column sums of dOut (K). Partials per range of
+ *   rows in the workspace (crb_head_bn_workspace_bytes), added in range order in double. Two launches.
+ * crb_head_bn_finalize: sums, W, par -> dgb (2, Ct) = dbeta | dgamma, dw (K, Ct), dbias (K) (NULL: not written), in double. One launch.
+ * crb_head_bn_weights: image (crb_head_bn_weights_bytes) of W for crb_head_bn_apply: [Ct / 32][ceil(K / 16)][piece 3][lane 64][8 bf16],
+ *   lane (r, h), element j of k step s holds W[16 s + 8 h + j][32 (c / 32) + r], zero past K.
+ * crb_head_bn_apply: -> dx0, dx1 (n, width), bn_bwd_apply_kernel's expression on dz formed in accumulators. One launch. */
+int crb_head_bn_supported(int nbranch, int width, int K);
+int64_t crb_head_bn_workspace_bytes(int nbranch, int width, int K);
+int64_t crb_head_bn_sums_count(int nbranch, int width, int K);
+int crb_head_bn_sums(const float* x0, const float* x1, const float* par, const float* dout, int64_t n, int nbranch, int width, int K,
+                     double* sums, void* workspace, int64_t workspace_bytes, void* stream);
+int crb_head_bn_finalize(const double* sums, const float* w, const float* par, int nbranch, int width, int K, float* dgb, float* dw,
+                         float* dbias, void* stream);
+int64_t crb_head_bn_weights_bytes(int nbranch, int width, int K);
+int crb_head_bn_weights(const float* w, void* image, int nbranch, int width, int K, void* stream);
+int crb_head_bn_apply(const float* x0, const float* x1, const float* par, const float* dgb, const float* dout, const void* image,
+                      int64_t n, int nbranch, int width, int K, float* dx0, float* dx1, void* stream);
+
 /* Scheduling hint, no reference counterpart: PV-RCNN's keypoint sampling (crb_furthest_point_sampling_stack on a side stream under
  * the backbones) holds one CU per frame for ~5 ms while the persistent one-workgroup-per-CU Winograd launches of the BEV backbone
  * run on the main stream. crb_cu_reservation(cus, stream) right before such a kernel, crb_cu_reservation(0, stream) right after it
