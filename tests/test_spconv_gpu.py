@@ -224,11 +224,15 @@ def test_empty_and_tiny_inputs(dev):
         x = torch.randn(len(coords), 16, device=dev, requires_grad=True)
         w = torch.randn(27, 16, 16, device=dev, requires_grad=True)
         y = sparse.sparse_conv(x, w, rb)
-        y.sum().backward()
+        dY = torch.randn(len(coords), 16, device=dev)
+        y.backward(dY)
         assert y.shape == (len(coords), 16)
         if len(coords):
             nbr = oracle.subm_nbr(coords, shape, [3, 3, 3])
-            _close(y.detach().cpu().numpy(), oracle.conv_fwd(x.detach().cpu().numpy(), w.detach().cpu().numpy(), nbr))
+            xn, wn, gn = x.detach().cpu().numpy(), w.detach().cpu().numpy(), dY.cpu().numpy()
+            _close(y.detach().cpu().numpy(), oracle.conv_fwd(xn, wn, nbr))
+            _close(x.grad.cpu().numpy(), oracle.conv_dgrad(gn, wn, nbr, len(coords)))
+            _close(w.grad.cpu().numpy(), oracle.conv_wgrad(xn, gn, nbr, 27))
         else:
             assert float(w.grad.abs().sum()) == 0.0
 
