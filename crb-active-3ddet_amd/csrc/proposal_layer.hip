@@ -9,6 +9,8 @@
 //       73-108: rois / roi_scores / roi_labels of the kept boxes, zero padding)
 // ~45 elementwise / gather launches over (B, 9000, .) tensors in training, (B, 1024, .) in the scoring pass.
 // Every operation is the f32 operation of the torch expression in the same order (-ffp-contract=off): results equal it bit for bit.
+// That includes limit_period's `val / period`: ATen divides a device tensor by a host scalar as val * (1 / period), and within an ulp
+// of a multiple of the period the two quotients fall on different sides of the integer, which moves the heading by a whole period.
 #include "crb_common.h"
 #include "../../include/crb_hip.h"
 
@@ -17,7 +19,7 @@ namespace {
 __global__ __launch_bounds__(256) void decode_selected_kernel(const float* __restrict__ box, const float* __restrict__ dir,
                                                               const float* __restrict__ anchors, const int64_t* __restrict__ idx, int B,
                                                               int64_t A, int k, int nb, float dir_offset, float dir_limit_offset,
-                                                              float period, float* __restrict__ out) {
+                                                              float period, float inv_period, float* __restrict__ out) {
   const int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x;
   if (t >= (int64_t)B * k) return;
   const int b = (int)(t / k);
@@ -40,7 +42,7 @@ __global__ __launch_bounds__(256) void decode_selected_kernel(const float* __res
     for (int j = 1; j < nb; ++j)
       if (d[j] > best) { best = d[j]; lab = j; }
     const float v = r - dir_offset;
-    const float dir_rot = v - floorf(v / period + dir_limit_offset) * period;
+    const float dir_rot = v - floorf(v * inv_period + dir_limit_offset) * period;
     r = dir_rot + dir_offset + period * (float)lab;
   }
   o[6] = r;
@@ -75,8 +77,9 @@ extern "C" int crb_decode_selected_anchors(const float* box_preds, const float* 
   if (k == 0) return CRB_OK;
   if (!box_preds || !anchors || !anchor_idx || !out) return CRB_ERR_ARG;
   const float period = dir_preds ? (float)(2.0 * 3.14159265358979323846 / (double)num_dir_bins) : 0.f;
+  const float inv_period = dir_preds ? 1.0f / period : 0.f;
   hipLaunchKernelGGL(decode_selected_kernel, dim3(crb_cdiv((int64_t)B * k, 256)), dim3(256), 0, (hipStream_t)stream, box_preds, dir_preds,
-                     anchors, anchor_idx, B, A, k, num_dir_bins, dir_offset, dir_limit_offset, period, out);
+                     anchors, anchor_idx, B, A, k, num_dir_bins, dir_offset, dir_limit_offset, period, inv_period, out);
   CRB_CHECK_LAUNCH();
   return CRB_OK;
 }

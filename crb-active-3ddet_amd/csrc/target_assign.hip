@@ -20,6 +20,7 @@
 namespace {
 
 constexpr int MAXG = 1024;    // ground truths per frame staged in LDS
+constexpr int MAXC = 64;      // class ids 1 .. MAXC - 1: one presence flag per id in LDS (n_thr = largest id + 1 <= MAXC)
 
 struct Aligned { float x1, y1, x2, y2; };
 
@@ -47,28 +48,29 @@ __device__ __forceinline__ float iou_aligned(const Aligned& a, const Aligned& b)
 
 // anchors (A,7) in the flattened (z,y,x,class,size,rot) order, anchor_cls (A) i32 1-based class of every anchor
 // gt (B,G,8) zero padded; gvalid (B,G) u8: rows up to the last non-zero row
+// matched / unmatched: n_thr entries indexed by class id; a ground truth whose id is outside 1 .. n_thr - 1 belongs to no anchor class
 template <int PASS>
 __global__ __launch_bounds__(256) void assign_kernel(const float* __restrict__ anchors, const int* __restrict__ anchor_cls,
                                                      int A, const float* __restrict__ gt, const unsigned char* __restrict__ gvalid,
                                                      int G, const float* __restrict__ matched, const float* __restrict__ unmatched,
-                                                     int* __restrict__ g2a_max /* (B,G) IoU bits */,
+                                                     int n_thr, int* __restrict__ g2a_max /* (B,G) IoU bits */,
                                                      int* __restrict__ best_gt /* (B,A) */, float* __restrict__ best_iou,
                                                      int* __restrict__ labels, float* __restrict__ targets,
                                                      float* __restrict__ reg_weights) {
   __shared__ Aligned sg[MAXG];
   __shared__ int scls[MAXG];
   __shared__ int smax[MAXG];       // pass 1: this block's running max per gt; pass 2: the global max
-  __shared__ int has_cls[8];
+  __shared__ int has_cls[MAXC];
   const int b = blockIdx.y;
   const float* fg = gt + (int64_t)b * G * 8;
-  if (threadIdx.x < 8) has_cls[threadIdx.x] = 0;
+  if (threadIdx.x < MAXC) has_cls[threadIdx.x] = 0;
   __syncthreads();
   for (int g = threadIdx.x; g < G; g += 256) {
     const float* q = fg + g * 8;
     sg[g] = aligned_bev(q[0], q[1], q[3], q[4], q[6]);
     const int c = gvalid[(int64_t)b * G + g] ? (int)q[7] : 0;
     scls[g] = c;
-    if (c > 0 && c < 8) has_cls[c] = 1;
+    if (c > 0 && c < n_thr) has_cls[c] = 1;
     smax[g] = (PASS == 2) ? g2a_max[(int64_t)b * G + g] : 0;
   }
   __syncthreads();
@@ -107,9 +109,10 @@ __global__ __launch_bounds__(256) void assign_kernel(const float* __restrict__ a
       if (mx <= 0) continue;                                   // best overlap 0: the reference sets it to -1 (never equal)
       forced |= (__float_as_int(iou_aligned(ab, sg[g])) == mx);
     }
-    const bool any_gt = has_cls[cls & 7] != 0;
+    const bool known = cls > 0 && cls < n_thr;               // an anchor class without thresholds gets no positives
+    const bool any_gt = known && has_cls[cls] != 0;
     const bool fgf = any_gt && (forced || best >= matched[cls]);
-    const bool bgf = (best < unmatched[cls]) && !forced;
+    const bool bgf = known && (best < unmatched[cls]) && !forced;
     int lab = fgf ? cls : (bgf ? 0 : -1);
     if (!any_gt) lab = 0;
     labels[o] = lab;
@@ -142,10 +145,10 @@ extern "C" int64_t crb_assign_targets_workspace_bytes(int B, int A, int G) {
 
 extern "C" int crb_assign_targets(const float* anchors, const int32_t* anchor_cls, int A, const float* gt_boxes,
                                   const uint8_t* gt_valid, int B, int G, const float* matched_thr,
-                                  const float* unmatched_thr, int32_t* labels, float* reg_targets, float* reg_weights,
+                                  const float* unmatched_thr, int n_thr, int32_t* labels, float* reg_targets, float* reg_weights,
                                   void* workspace, int64_t workspace_bytes, void* stream) {
-  if (A <= 0 || B <= 0 || G <= 0) return CRB_ERR_ARG;
-  if (G > MAXG) return CRB_ERR_UNSUPPORTED;
+  if (A <= 0 || B <= 0 || G <= 0 || n_thr <= 1) return CRB_ERR_ARG;
+  if (G > MAXG || n_thr > MAXC) return CRB_ERR_UNSUPPORTED;
   CrbArena a(workspace, (size_t)workspace_bytes);
   int* g2a = a.take<int>((int64_t)B * G);
   int* best_gt = a.take<int>((int64_t)B * A);
@@ -155,9 +158,9 @@ extern "C" int crb_assign_targets(const float* anchors, const int32_t* anchor_cl
   CRB_HIP(hipMemsetAsync(g2a, 0, sizeof(int) * (size_t)B * G, st));
   dim3 grid(crb_cdiv(A, 256), B);
   hipLaunchKernelGGL(assign_kernel<1>, grid, dim3(256), 0, st, anchors, anchor_cls, A, gt_boxes, gt_valid, G, matched_thr,
-                     unmatched_thr, g2a, best_gt, best_iou, labels, reg_targets, reg_weights);
+                     unmatched_thr, n_thr, g2a, best_gt, best_iou, labels, reg_targets, reg_weights);
   hipLaunchKernelGGL(assign_kernel<2>, grid, dim3(256), 0, st, anchors, anchor_cls, A, gt_boxes, gt_valid, G, matched_thr,
-                     unmatched_thr, g2a, best_gt, best_iou, labels, reg_targets, reg_weights);
+                     unmatched_thr, n_thr, g2a, best_gt, best_iou, labels, reg_targets, reg_weights);
   CRB_CHECK_LAUNCH();
   return CRB_OK;
 }

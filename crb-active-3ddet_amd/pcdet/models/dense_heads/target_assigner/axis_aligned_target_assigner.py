@@ -17,6 +17,10 @@ from crbhip import lib, check, ptr, cur_stream
 from ....utils import box_utils
 
 FUSED = True      # use the two-launch HIP assigner (crb_assign_targets) for device tensors; False = batched torch ops
+# limits of csrc/target_assign.hip (MAXG ground-truth rows staged in LDS, MAXC - 1 = largest class id with a presence flag):
+# beyond them the batched torch ops below do the work
+FUSED_MAX_GT = 1024
+FUSED_MAX_CLASS_ID = 63
 
 
 class AxisAlignedTargetAssigner(object):
@@ -34,6 +38,7 @@ class AxisAlignedTargetAssigner(object):
         self.matched_thresholds = {c['class_name']: c['matched_threshold'] for c in anchor_generator_cfg}
         self.unmatched_thresholds = {c['class_name']: c['unmatched_threshold'] for c in anchor_generator_cfg}
         self.use_multihead = model_cfg.get('USE_MULTIHEAD', False)
+        self.max_class_id = max(int(np.nonzero(self.class_names == n)[0][0]) + 1 for n in self.anchor_class_names)
         if self.pos_fraction is not None or self.use_multihead or self.match_height:
             raise NotImplementedError('only POS_FRACTION<0, single head, nearest-BEV matching are on the hot path')
 
@@ -41,9 +46,16 @@ class AxisAlignedTargetAssigner(object):
         """all_anchors: [(nz,ny,nx,S,R,7) per class]; gt (B,G,8) zero padded, last column class id 1..C
         -> box_cls_labels (B,A) int32, box_reg_targets (B,A,code), reg_weights (B,A); A ordered (z,y,x,class,size,rot)"""
         gt = gt_boxes_with_classes
-        if FUSED and gt.is_cuda and self.box_coder.code_size == 7 and not self.norm_by_num_examples:
-            return self.assign_targets_fused(all_anchors, gt)
         B, G = gt.shape[0], gt.shape[1]
+        if G == 0:
+            # no ground-truth rows at all: every (frame, class) pair is the reference's "no gt of this class" case
+            A = sum(a.numel() // a.shape[-1] for a in all_anchors)
+            return {'box_cls_labels': torch.zeros((B, A), dtype=torch.int32, device=gt.device),
+                    'box_reg_targets': torch.zeros((B, A, self.box_coder.code_size), dtype=torch.float32, device=gt.device),
+                    'reg_weights': torch.zeros((B, A), dtype=torch.float32, device=gt.device)}
+        if FUSED and gt.is_cuda and self.box_coder.code_size == 7 and not self.norm_by_num_examples and G <= FUSED_MAX_GT \
+                and self.max_class_id <= FUSED_MAX_CLASS_ID:
+            return self.assign_targets_fused(all_anchors, gt)
         gt_boxes, gt_cls = gt[..., :-1], gt[..., -1]
         # valid = everything up to the last non-zero row (axis_aligned_target_assigner.py:54-58; row 0 always kept)
         nonzero = gt_boxes.sum(-1) != 0
@@ -109,7 +121,7 @@ class AxisAlignedTargetAssigner(object):
         wsb = lib.crb_assign_targets_workspace_bytes(B, A, G)
         ws = torch.empty((wsb,), dtype=torch.uint8, device=dev)
         check(lib.crb_assign_targets(ptr(anchors), ptr(anchor_cls), A, ptr(gtc), ptr(valid), B, G, ptr(m), ptr(u),
-                                     ptr(labels), ptr(targets), ptr(weights), ptr(ws), wsb, cur_stream(dev)),
+                                     int(m.numel()), ptr(labels), ptr(targets), ptr(weights), ptr(ws), wsb, cur_stream(dev)),
               'crb_assign_targets')
         return {'box_cls_labels': labels, 'box_reg_targets': targets, 'reg_weights': weights}
 

@@ -680,13 +680,16 @@ int crb_bn_relu_max_forward_frames(const float* x, int n_frames, int64_t groups_
  *           axis_aligned_target_assigner.py:36-210), box_utils.boxes3d_nearest_bev_iou (pcdet/utils/box_utils.py:272-298),
  *           ResidualCoder.encode_torch (pcdet/utils/box_coder_utils.py:13-43); POS_FRACTION < 0 branch, single head.
  * anchors (A,7) in the head's flattened order with anchor_cls (A) i32 (1-based class); gt_boxes (B,G,8) zero padded,
- * gt_valid (B,G) u8; matched_thr / unmatched_thr: device f32 arrays indexed by class id (entry 0 unused).
+ * gt_valid (B,G) u8; matched_thr / unmatched_thr: device f32 arrays of n_thr entries indexed by class id (entry 0 unused,
+ * n_thr = largest class id + 1); a ground truth whose class id is outside 1 .. n_thr - 1 matches no anchor.
  * out: labels (B,A) i32 {-1,0,class}, reg_targets (B,A,7), reg_weights (B,A).
+ * Limits: 1 <= G <= 1024 ground-truth rows per frame and n_thr <= 64 (class ids 1 .. 63), else CRB_ERR_UNSUPPORTED; G == 0 is
+ * CRB_ERR_ARG (nothing to launch: every label, target and weight is 0, which the caller writes itself).
  * ---------------------------------------------------------------------------------------------- */
 int64_t crb_assign_targets_workspace_bytes(int B, int A, int G);
 int crb_assign_targets(const float* anchors, const int32_t* anchor_cls, int A, const float* gt_boxes,
                        const uint8_t* gt_valid, int B, int G, const float* matched_thr,
-                       const float* unmatched_thr, int32_t* labels, float* reg_targets, float* reg_weights,
+                       const float* unmatched_thr, int n_thr, int32_t* labels, float* reg_targets, float* reg_weights,
                        void* workspace, int64_t workspace_bytes, void* stream);
 
 /* ------------------------------------------------------------------------------------------------

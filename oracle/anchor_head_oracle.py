@@ -145,12 +145,14 @@ def focal_loss(logits, targets, weights, alpha=0.25, gamma=2.0):
 def smooth_l1(pred, target, weights, beta=1.0 / 9.0):
     target = torch.where(torch.isnan(target), pred, target)
     n = torch.abs(pred - target)
+    if beta < 1e-5:          # pure L1 (loss_utils.py:101-102): the quadratic branch would divide by beta
+        return n * weights.unsqueeze(-1)
     loss = torch.where(n < beta, 0.5 * n ** 2 / beta, n - 0.5 * beta)
     return loss * weights.unsqueeze(-1)
 
 
 def rpn_loss(cls_preds, box_preds, dir_preds, labels, reg_targets, anchors_list, num_class=3, dir_offset=0.78539,
-             num_bins=2, w_cls=1.0, w_loc=2.0, w_dir=0.2):
+             num_bins=2, w_cls=1.0, w_loc=2.0, w_dir=0.2, alpha=0.25, gamma=2.0, beta=1.0 / 9.0):
     """cls_preds (B,H,W,A*C), box_preds (B,H,W,A*7), dir_preds (B,H,W,A*bins) -> total, cls, loc, dir"""
     B = cls_preds.shape[0]
     cared = labels >= 0
@@ -163,11 +165,11 @@ def rpn_loss(cls_preds, box_preds, dir_preds, labels, reg_targets, anchors_list,
     tgt = (labels * cared.type_as(labels)).long()
     one_hot = torch.zeros(*tgt.shape, num_class + 1)
     one_hot.scatter_(-1, tgt.unsqueeze(-1), 1.0)
-    cls_loss = focal_loss(cls_preds.view(B, -1, num_class), one_hot[..., 1:], cls_w).sum() / B * w_cls
+    cls_loss = focal_loss(cls_preds.view(B, -1, num_class), one_hot[..., 1:], cls_w, alpha, gamma).sum() / B * w_cls
     bp = box_preds.view(B, -1, 7)
     sin_p = torch.sin(bp[..., 6:7]) * torch.cos(reg_targets[..., 6:7])
     sin_t = torch.cos(bp[..., 6:7]) * torch.sin(reg_targets[..., 6:7])
-    loc = smooth_l1(torch.cat([bp[..., :6], sin_p], -1), torch.cat([reg_targets[..., :6], sin_t], -1), reg_w)
+    loc = smooth_l1(torch.cat([bp[..., :6], sin_p], -1), torch.cat([reg_targets[..., :6], sin_t], -1), reg_w, beta)
     loc_loss = loc.sum() / B * w_loc
     anchors = torch.cat(anchors_list, dim=-3).view(1, -1, 7).repeat(B, 1, 1)
     rot_gt = reg_targets[..., 6] + anchors[..., 6]
