@@ -43,8 +43,7 @@ __device__ __forceinline__ bool seg_cross(P2 p1, P2 p0, P2 q1, P2 q0, P2& out) {
   return true;
 }
 
-__device__ __forceinline__ bool in_box_margin(const float* b, P2 p) {
-  const float margin = 1e-2f;
+__device__ __forceinline__ bool in_box_margin(const float* b, P2 p, float margin) {
   float ac = cosf(-b[6]), as = sinf(-b[6]);
   float rx = (p.x - b[0]) * ac + (p.y - b[1]) * (-as);
   float ry = (p.x - b[0]) * as + (p.y - b[1]) * ac;
@@ -66,8 +65,10 @@ __device__ __forceinline__ void box_corners(const float* b, P2* c /*5*/) {
   c[4] = c[0];
 }
 
-// rotated-rectangle intersection area (reference: box_overlap, iou3d_nms_kernel.cu:104-225)
-__device__ float rect_overlap(const float* a, const float* b) {
+// rotated-rectangle intersection area (reference: box_overlap, iou3d_nms_kernel.cu:104-225). margin: how far outside a box a corner of
+// the other one still counts as inside. The reference's NMS uses 1e-2 (a centimetre); csrc/kitti_eval.hip, whose bar is an f64
+// overlap, passes boxes translated to their own neighbourhood and a margin just above their f32 rounding.
+__device__ float rect_overlap(const float* a, const float* b, const float margin = 1e-2f) {
   P2 ca[5], cb[5];
   box_corners(a, ca);
   box_corners(b, cb);
@@ -83,8 +84,8 @@ __device__ float rect_overlap(const float* a, const float* b) {
       }
     }
   for (int k = 0; k < 4; ++k) {
-    if (in_box_margin(a, cb[k])) { sx = sx + cb[k].x; sy = sy + cb[k].y; pts[cnt++] = cb[k]; }
-    if (in_box_margin(b, ca[k])) { sx = sx + ca[k].x; sy = sy + ca[k].y; pts[cnt++] = ca[k]; }
+    if (in_box_margin(a, cb[k], margin)) { sx = sx + cb[k].x; sy = sy + cb[k].y; pts[cnt++] = cb[k]; }
+    if (in_box_margin(b, ca[k], margin)) { sx = sx + ca[k].x; sy = sy + ca[k].y; pts[cnt++] = ca[k]; }
   }
   float cx = sx / cnt, cy = sy / cnt;    // cnt == 0 -> NaN centre, loops below do nothing, area 0 (as the reference)
   // bubble sort by polar angle about the centroid (same comparison sequence as the reference => same permutation)

@@ -144,3 +144,89 @@ def random_sparse_coords(rng, n, batch_size, shape_dhw, clustered=True):
     _, first = np.unique(pts, axis=0, return_index=True)
     pts = pts[np.sort(first)][:n]
     return np.ascontiguousarray(pts.astype(np.int32))
+
+
+# --- evaluation side of the synthetic KITTI frames: one fixed KITTI-like calibration and the frames' ground truth in KITTI form ---
+KITTI_P2 = [[721.5377, 0.0, 609.5593, 44.85728], [0.0, 721.5377, 172.854, 0.2163791], [0.0, 0.0, 1.0, 0.002745884]]
+KITTI_R0 = [[0.9999239, 0.00983776, -0.007445048], [-0.009869795, 0.9999421, -0.004278459], [0.007402527, 0.004351614, 0.9999631]]
+KITTI_TR_VELO2CAM = [[0.007533745, -0.9999714, -0.000616602, -0.004069766], [0.01480249, 0.0007280733, -0.9998902, -0.07631618],
+                     [0.9998621, 0.00752379, 0.01480755, -0.2717806]]
+KITTI_IMAGE_SHAPE = (375, 1242)                     # (height, width)
+KITTI_CLASS_NAMES = ('Car', 'Pedestrian', 'Cyclist')    # class ids 1, 2, 3 of kitti_frame's boxes
+TRUNCATION_LEVELS = (0.0, 0.2, 0.4, 0.6)
+
+
+class Calibration(object):
+    """the reference Calibration's coordinate changes (pcdet/utils/calibration_kitti.py) for matrices P2 (3, 4), R0 (3, 3),
+    Tr_velo2cam (3, 4); f64 unless the matrices are given in another type. Without arguments: the synthetic frames' calibration."""
+
+    def __init__(self, calib=None):
+        calib = calib or {'P2': np.array(KITTI_P2), 'R0': np.array(KITTI_R0), 'Tr_velo2cam': np.array(KITTI_TR_VELO2CAM)}
+        self.P2, self.R0, self.V2C = calib['P2'], calib['R0'], calib['Tr_velo2cam']
+        self.cu, self.cv, self.fu, self.fv = self.P2[0, 2], self.P2[1, 2], self.P2[0, 0], self.P2[1, 1]
+        self.tx, self.ty = self.P2[0, 3] / (-self.fu), self.P2[1, 3] / (-self.fv)
+
+    @staticmethod
+    def cart_to_hom(pts):
+        return np.hstack((pts, np.ones((pts.shape[0], 1), dtype=pts.dtype)))
+
+    def lidar_to_rect(self, pts_lidar):
+        return self.cart_to_hom(pts_lidar) @ (self.V2C.T @ self.R0.T)
+
+    def rect_to_lidar(self, pts_rect):
+        m = np.eye(4, dtype=self.R0.dtype)
+        m[:3, :3] = self.R0
+        v = np.eye(4, dtype=self.V2C.dtype)
+        v[:3] = self.V2C
+        return (self.cart_to_hom(pts_rect) @ np.linalg.inv((m @ v).T))[:, 0:3]
+
+    def rect_to_img(self, pts_rect):
+        """-> pixel coordinates (N, 2), depth in the rect camera frame (N)"""
+        hom = self.cart_to_hom(pts_rect) @ self.P2.T
+        return hom[:, 0:2] / pts_rect[:, 2:3], hom[:, 2] - self.P2[2, 3]
+
+    def lidar_to_img(self, pts_lidar):
+        return self.rect_to_img(self.lidar_to_rect(pts_lidar))
+
+    def img_to_rect(self, u, v, depth_rect):
+        x = ((u - self.cu) * depth_rect) / self.fu + self.tx
+        y = ((v - self.cv) * depth_rect) / self.fv + self.ty
+        return np.stack([x, y, depth_rect], axis=1)
+
+
+def kitti_frame_boxes(frame_idx):
+    """the gt_boxes of kitti_frame(frame_idx) without its points (the boxes are the generator's first draws)"""
+    rng = np.random.default_rng(np.random.PCG64(20230501 + int(frame_idx)))
+    return _boxes(rng, 6, 3, 3, (5, 65), (-30, 30), -1.73)
+
+
+def kitti_frame_annos(frame_idx):
+    """ground truth of a synthetic KITTI frame as a KITTI anno dict, from its lidar boxes through the calibration above:
+    location / dimensions (l, h, w) / rotation_y in the rect camera frame, bbox the clipped projection, alpha = -atan2(-y, x) + ry
+    (lidar x, y). Occlusion and truncation are not in the scene; they follow the indices so that every difficulty occurs:
+    Boxes the camera does not see are left out ('index': the rows of kitti_frame's gt_boxes that are kept).
+    occluded = (frame + box) % 4 and truncated = TRUNCATION_LEVELS[occluded], so a quarter of the boxes can count as easy, a quarter
+    from moderate on, a quarter as hard only and a quarter never (the image-box height decides the rest)."""
+    from ..utils import box_utils
+    boxes = kitti_frame_boxes(frame_idx).astype(np.float64)
+    calib = Calibration()
+    cam = box_utils.boxes3d_lidar_to_kitti_camera(boxes[:, :7], calib)
+    bbox = box_utils.boxes3d_kitti_camera_to_imageboxes(cam, calib, image_shape=KITTI_IMAGE_SHAPE)
+    # KITTI labels what the camera sees: a box whose clipped projection has no area (beside or behind the image) is left out
+    seen = np.nonzero((cam[:, 2] > 0) & (bbox[:, 2] > bbox[:, 0]) & (bbox[:, 3] > bbox[:, 1]))[0]
+    boxes, cam, bbox = boxes[seen], cam[seen], bbox[seen]
+    level = (int(frame_idx) + seen) % 4
+    return {'name': np.array(KITTI_CLASS_NAMES)[boxes[:, 7].astype(np.int64) - 1], 'truncated': np.array(TRUNCATION_LEVELS)[level],
+            'occluded': level.astype(np.int64), 'alpha': -np.arctan2(-boxes[:, 1], boxes[:, 0]) + cam[:, 6], 'bbox': bbox,
+            'dimensions': cam[:, 3:6], 'location': cam[:, 0:3], 'rotation_y': cam[:, 6], 'score': -np.ones(len(boxes)),
+            'gt_boxes_lidar': boxes[:, :7], 'index': seen}
+
+
+class FrameInfo(dict):
+    """an entry of kitti_infos; info['annos'] of a KITTI frame is made on first use and kept"""
+
+    def __missing__(self, key):
+        if key != 'annos' or self.get('kind', 'kitti') != 'kitti':
+            raise KeyError(key)
+        self['annos'] = kitti_frame_annos(self['frame_id'])
+        return self['annos']

@@ -56,7 +56,9 @@ class SyntheticDataset(Dataset):
         self.grid_size = np.round(g).astype(np.int64)
         self.depth_downsample_factor = None
         self.sample_id_list = ['%06d' % (first_frame + i) for i in range(num_frames)]
-        self.kitti_infos = [{'point_cloud': {'lidar_idx': s}, 'frame_id': s} for s in self.sample_id_list]
+        # (KITTI kind: info['annos'], the frame's ground truth in KITTI form, appears on first use - syn.FrameInfo)
+        info = syn.FrameInfo if kind == 'kitti' else dict
+        self.kitti_infos = [info({'point_cloud': {'lidar_idx': s}, 'frame_id': s}) for s in self.sample_id_list]
         self.frame_ids = self.sample_id_list
         self.infos = self.kitti_infos
         self._voxel_generator = None
@@ -137,6 +139,66 @@ class SyntheticDataset(Dataset):
             self.sample_id_list, self.kitti_infos = self.frame_ids, self.infos
         else:
             self.frame_ids, self.infos = self.sample_id_list, self.kitti_infos
+
+    @property
+    def calib(self):
+        """the one calibration of the synthetic KITTI frames (syn.Calibration); image_shape next to it"""
+        if self.kind != 'kitti':
+            raise NotImplementedError('the synthetic Waymo frames have no camera: calib / image_shape exist for kind="kitti" only')
+        if getattr(self, '_calib', None) is None:
+            self._calib = syn.Calibration()
+        return self._calib
+
+    @property
+    def image_shape(self):
+        self.calib
+        return np.array(syn.KITTI_IMAGE_SHAPE, dtype=np.int32)
+
+    def generate_prediction_dicts(self, batch_dict, pred_dicts, class_names, output_path=None):
+        """KittiDataset.generate_prediction_dicts (pcdet/datasets/kitti/kitti_dataset.py:277-351): per frame the ten KITTI keys
+        + frame_id from pred_boxes / pred_scores / pred_labels; a frame without boxes keeps the reference's template, whose `name`
+        is np.zeros(0). output_path: a directory that receives <frame_id>.txt label files in the reference's format.
+        calib and image_shape come from the dataset, not from the batch."""
+        from ..utils import box_utils
+        calib, image_shape = self.calib, self.image_shape
+        to_np = lambda v: (v[0] if isinstance(v, list) else v).detach().cpu().numpy() if not isinstance(v, np.ndarray) else v
+        annos = []
+        for index, box_dict in enumerate(pred_dicts):
+            scores, boxes, labels = (to_np(box_dict[k]) for k in ('pred_scores', 'pred_boxes', 'pred_labels'))
+            n = scores.shape[0]
+            d = {'name': np.zeros(n), 'truncated': np.zeros(n), 'occluded': np.zeros(n), 'alpha': np.zeros(n), 'bbox': np.zeros([n, 4]),
+                 'dimensions': np.zeros([n, 3]), 'location': np.zeros([n, 3]), 'rotation_y': np.zeros(n), 'score': np.zeros(n),
+                 'boxes_lidar': np.zeros([n, 7])}
+            if n:
+                cam = box_utils.boxes3d_lidar_to_kitti_camera(boxes, calib)
+                d.update({'name': np.array(class_names)[labels.astype(np.int64) - 1],
+                          'alpha': -np.arctan2(-boxes[:, 1], boxes[:, 0]) + cam[:, 6],
+                          'bbox': box_utils.boxes3d_kitti_camera_to_imageboxes(cam, calib, image_shape=image_shape),
+                          'dimensions': cam[:, 3:6], 'location': cam[:, 0:3], 'rotation_y': cam[:, 6], 'score': scores,
+                          'boxes_lidar': boxes})
+            d['frame_id'] = batch_dict['frame_id'][index]
+            annos.append(d)
+            if output_path is not None:
+                import os
+                with open(os.path.join(str(output_path), '%s.txt' % d['frame_id']), 'w') as f:
+                    bbox, loc, dims = d['bbox'], d['location'], d['dimensions']          # dims: lhw -> hwl in the file
+                    for i in range(len(bbox)):
+                        print('%s -1 -1 %.4f %.4f %.4f %.4f %.4f %.4f %.4f %.4f %.4f %.4f %.4f %.4f %.4f'
+                              % (d['name'][i], d['alpha'][i], bbox[i][0], bbox[i][1], bbox[i][2], bbox[i][3], dims[i][1], dims[i][2],
+                                 dims[i][0], loc[i][0], loc[i][1], loc[i][2], d['rotation_y'][i], d['score'][i]), file=f)
+        return annos
+
+    def evaluation(self, det_annos, class_names, **kwargs):
+        """-> (ap_result_str, ap_dict) of det_annos (one per entry of kitti_infos, in its order) against the frames' ground truth
+        through pcdet.datasets.kitti.kitti_object_eval_python (kwargs: route='device' | 'host', PR_detail_dict=, detail=)"""
+        if self.kind != 'kitti':
+            raise NotImplementedError('only the KITTI metrics are provided: the Waymo metrics of the reference need TensorFlow '
+                                      '(waymo_open_dataset), which this stack does not have')
+        import copy
+        from .kitti.kitti_object_eval_python import eval as kitti_eval
+        gt_annos = [copy.deepcopy(info['annos']) for info in self.kitti_infos]
+        keep = {k: kwargs[k] for k in ('route', 'PR_detail_dict', 'detail') if k in kwargs}
+        return kitti_eval.get_official_eval_result(gt_annos, copy.deepcopy(det_annos), class_names, **keep)
 
     @property
     def mode(self):

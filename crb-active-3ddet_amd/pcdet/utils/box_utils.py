@@ -75,3 +75,38 @@ def mask_boxes_outside_range_numpy(boxes, limit_range, min_num_corners=1):
     lr = np.asarray(limit_range, dtype=np.float32)
     mask = ((corners >= lr[0:3]) & (corners <= lr[3:6])).all(axis=2)
     return mask.sum(axis=1) >= min_num_corners
+
+
+# --- KITTI camera-frame boxes (pcdet/utils/box_utils.py:161-246); numpy, the evaluation hooks of the datasets use them ---
+def boxes3d_lidar_to_kitti_camera(boxes3d_lidar, calib):
+    """(N, 7) [x, y, z, dx, dy, dz, heading] with the box centre -> (N, 7) [x, y, z, l, h, w, r] in rect camera coordinates with
+    (x, y, z) the centre of the bottom face; r = -heading - pi / 2"""
+    boxes = np.array(boxes3d_lidar, copy=True)
+    bottom = boxes[:, 0:3]
+    bottom[:, 2] -= boxes[:, 5] / 2
+    return np.concatenate([calib.lidar_to_rect(bottom), boxes[:, 3:4], boxes[:, 5:6], boxes[:, 4:5], -boxes[:, 6:7] - np.pi / 2], axis=-1)
+
+
+def boxes3d_to_corners3d_kitti_camera(boxes3d, bottom_center=True):
+    """(N, 7) [x, y, z, l, h, w, ry] in camera coordinates -> (N, 8, 3); corners 0-3 the bottom face (y points down), 4-7 the top
+    face above them, in the reference's order"""
+    boxes3d = np.asarray(boxes3d)
+    l, h, w, ry = boxes3d[:, 3:4], boxes3d[:, 4:5], boxes3d[:, 5:6], boxes3d[:, 6:7]
+    x = l / 2 * np.array([[1., 1., -1., -1., 1., 1., -1., -1.]])
+    z = w / 2 * np.array([[1., -1., -1., 1., 1., -1., -1., 1.]])
+    y = h * (np.array([[0., 0., 0., 0., -1., -1., -1., -1.]]) if bottom_center else np.array([[.5, .5, .5, .5, -.5, -.5, -.5, -.5]]))
+    c, s = np.cos(ry), np.sin(ry)
+    corners = np.stack([x * c + z * s, y, -x * s + z * c], axis=2)
+    return corners + boxes3d[:, None, 0:3]
+
+
+def boxes3d_kitti_camera_to_imageboxes(boxes3d, calib, image_shape=None):
+    """(N, 7) camera boxes -> (N, 4) [x1, y1, x2, y2]: the hull of the eight projected corners, clipped to the image when its
+    (height, width) is given"""
+    pts_img, _ = calib.rect_to_img(boxes3d_to_corners3d_kitti_camera(boxes3d).reshape(-1, 3))
+    uv = pts_img.reshape(-1, 8, 2)
+    boxes = np.concatenate([uv.min(axis=1), uv.max(axis=1)], axis=1)
+    if image_shape is not None:
+        boxes[:, 0::2] = np.clip(boxes[:, 0::2], 0, image_shape[1] - 1)
+        boxes[:, 1::2] = np.clip(boxes[:, 1::2], 0, image_shape[0] - 1)
+    return boxes

@@ -1404,6 +1404,57 @@ int crb_spc_plan(const float* points, int64_t n, int row_stride, const int32_t* 
 int crb_fps_segments(const float* xyz, int64_t rows, const int32_t* seg_table, const int32_t* num_segments, int max_segments,
                      int64_t out_capacity, float* temp, int32_t* out_idx, float* out_keypoints, void* stream);
 
+/* KITTI object AP: image / BEV / 3D overlaps, ignore flags, true-positive scores, score thresholds, precision-recall counts
+ * (csrc/kitti_eval.hip)
+ * replaces: rotate_iou_gpu_eval (pcdet/datasets/kitti/kitti_object_eval_python/rotate_iou.py, numba.cuda) and image_box_overlap,
+ *           d3_box_overlap_kernel, clean_data, compute_statistics_jit, get_thresholds, fused_compute_statistics of eval.py there
+ *           (numba.jit), with the per-frame / per-part Python loops of calculate_iou_partly and eval_class around them.
+ * Every call launches on `stream` and returns without waiting; nothing is read back between the calls.
+ * Layout: the boxes of all frames are stacked. gt_off / dt_off / pair_off (num_frames + 1) i64 prefix sums of the ground-truth boxes,
+ *   detections and (detection, ground truth) pairs of a frame; the pairs of frame f form a row-major [n_dt, n_gt] matrix at pair_off[f].
+ *   bbox (n, 4) f64 [x1, y1, x2, y2]; cam (n, 7) f64 [x, y, z, l, h, w, ry] in rect camera coordinates, y the bottom centre.
+ *   A combination q < num_combos is one (metric, class, difficulty, overlap row): combo_metric[q] in 0..2 (image, BEV, 3D),
+ *   combo_flags[q] = class index * 3 + difficulty (the row of gt_flag / dt_flag), combo_min_overlap[q] f64, combo_aos[q] = the slot of
+ *   its orientation-similarity sums in 0 .. num_aos - 1 or -1 for none.
+ * crb_kitti_overlaps: overlaps (4, num_pairs) f64 = image-box IoU (f64), BEV IoU (f32 arithmetic on the pair translated to the
+ *   ground-truth centre, positive ry clockwise), 3D IoU (BEV intersection x height overlap min(y1, y2) - max(y1 - h1, y2 - h2), zero
+ *   when not positive, union = sum of l h w minus the intersection; rounded to f32), image intersection over the detection's area
+ *   (the DontCare criterion).
+ * crb_kitti_ignore_flags: cls i32 0..5 = car, pedestrian, cyclist, van, person_sitting, truck, anything else for other names;
+ *   classes (num_classes) i32 device array of the evaluated classes; gt_flag (num_classes * 3, G) / dt_flag (num_classes * 3, D) i8:
+ *   0 counts, 1 ignored, -1 another class; difficulty limits as clean_data (<= on the ground-truth height, < on |height| of a detection).
+ * crb_kitti_match_scores: the compute_fp = False, thresh = 0 matching of every (frame, combination). tp_scores (num_combos, G) f64:
+ *   the matched detection's score in the slot of its ground-truth box, -inf elsewhere. asg_off (num_frames + 1) i64 prefix sums of
+ *   ceil(n_dt / 32); asg_workspace asg_off[num_frames] * num_combos u32.
+ * crb_kitti_thresholds: sorted_scores (num_combos, G) f64 descending with num_scores[q] leading entries, num_valid_gt (num_combos)
+ *   i32 -> thresholds (num_combos, 41) f64 and num_thresholds (num_combos) i32 by get_thresholds' skip rule.
+ * crb_kitti_match_pr: the compute_fp = True matching of every (frame, combination, threshold). gt_dc (G) u8 marks DontCare boxes.
+ *   Frames beyond crb_kitti_stage_limit (0: n_gt, 1: n_dt, 2: n_gt * n_dt) read global memory and keep their bits in asg_big:
+ *   big_off (num_frames + 1) i64 prefix sums of ceil(n_dt / 32) for those frames and 0 for the others, asg_big big_off[num_frames] *
+ *   num_combos * 64 u32. counts (num_combos, 41, 3) i32 and sim_part (num_frames, num_aos, 41) f64 are scratch.
+ *   result (num_combos * 41 * 5 + num_combos) f64: rows [tp, fp, fn, similarity, threshold] per (combination, threshold), then the
+ *   number of thresholds of every combination. Integer counts by integer atomics, the similarity summed over frames in frame order:
+ *   the same bits on every run. */
+int crb_kitti_stage_limit(int which);
+int crb_kitti_overlaps(const int64_t* gt_off, const int64_t* dt_off, const int64_t* pair_off, int64_t num_frames, int64_t num_pairs,
+                       const double* gt_bbox, const double* dt_bbox, const double* gt_cam, const double* dt_cam, double* overlaps,
+                       void* stream);
+int crb_kitti_ignore_flags(const int32_t* gt_cls, const double* gt_occ, const double* gt_trunc, const double* gt_bbox, int64_t G,
+                           const int32_t* dt_cls, const double* dt_bbox, int64_t D, const int32_t* classes, int num_classes,
+                           int8_t* gt_flag, int8_t* dt_flag, void* stream);
+int crb_kitti_match_scores(const int64_t* gt_off, const int64_t* dt_off, const int64_t* pair_off, const int64_t* asg_off,
+                           int64_t num_frames, int64_t G, int64_t D, int64_t num_pairs, const double* overlaps, const int8_t* gt_flag,
+                           const int8_t* dt_flag, const double* dt_score, const int32_t* combo_metric, const int32_t* combo_flags,
+                           const double* combo_min_overlap, int num_combos, uint32_t* asg_workspace, double* tp_scores, void* stream);
+int crb_kitti_thresholds(const double* sorted_scores, const int32_t* num_scores, const int32_t* num_valid_gt, int num_combos, int64_t G,
+                         double* thresholds, int32_t* num_thresholds, void* stream);
+int crb_kitti_match_pr(const int64_t* gt_off, const int64_t* dt_off, const int64_t* pair_off, const int64_t* big_off, int64_t num_frames,
+                       int64_t G, int64_t D, int64_t num_pairs, const double* overlaps, const int8_t* gt_flag, const int8_t* dt_flag,
+                       const double* dt_score, const uint8_t* gt_dc, const double* gt_alpha, const double* dt_alpha,
+                       const int32_t* combo_metric, const int32_t* combo_flags, const double* combo_min_overlap,
+                       const int32_t* combo_aos, int num_combos, int num_aos, const double* thresholds, const int32_t* num_thresholds,
+                       uint32_t* asg_big, int32_t* counts, double* sim_part, double* result, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
