@@ -8,6 +8,7 @@
 // ~55 elementwise / reduction launches over (32768, <= 4) tensors, ~3 us of device time each in the device-bound PV-RCNN step.
 // One workgroup: the positives are counted first (the normaliser), then every term and its derivative; sums in a fixed order.
 #include "crb_common.h"
+#include "focal_term.h"
 #include "../../include/crb_hip.h"
 
 namespace {
@@ -26,25 +27,7 @@ __device__ __forceinline__ float block_sum(float v, float* sh) {
   return t;
 }
 
-// focal term of one logit and its derivative w.r.t. the logit, the expressions of rpn_loss.hip (loss_utils.py:47-72)
-__device__ __forceinline__ void focal_term(float x, bool t, float alpha, float gamma, float& loss, float& d) {
-  const float p = 1.0f / (1.0f + expf(-x));
-  const float bce = fmaxf(x, 0.0f) - (t ? x : 0.0f) + log1pf(expf(-fabsf(x)));
-  const float pt = t ? 1.0f - p : p;
-  const float aw = t ? alpha : 1.0f - alpha;
-  float ptg, ptg1;
-  if (gamma == 2.0f) {
-    ptg = pt * pt;
-    ptg1 = 2.0f * pt;
-  } else {
-    ptg = powf(pt, gamma);
-    ptg1 = gamma * powf(pt, gamma - 1.0f);
-  }
-  loss = aw * ptg * bce;
-  const float dpt = t ? -p * (1.0f - p) : p * (1.0f - p);
-  const float dbce = x == 0.0f ? (t ? 0.0f : 1.0f) : (t ? p - 1.0f : p);
-  d = aw * (ptg1 * dpt * bce + ptg * dbce);
-}
+// (focal_term: focal_term.h, shared with csrc/part_head.hip)
 
 __global__ __launch_bounds__(TPB) void point_focal_loss_kernel(const float* __restrict__ preds, const int64_t* __restrict__ labels, int64_t n,
                                                                int C, float alpha, float gamma, float weight, float* __restrict__ out,

@@ -4,35 +4,16 @@
 // generate_pts_mask_for_box3d :39, collect_inside_pts_for_box3d :78, roiaware_{max,avg}pool3d :111/:160 and their
 // backward kernels :236/:261 (pybind surface roiaware_pool3d.cpp:172-177).
 //
-// Point-in-box test: |z-cz| <= dz/2 and the rotated |lx| < dx/2 + 1e-5, |ly| < dy/2 + 1e-5, evaluated like the
-// reference's device function (f32 sin/cos of -heading, the half-extent comparisons promoted to double by its
-// `/ 2.0` literals, roiaware_pool3d_kernel.cu:23-36).
+// Point-in-box test: pt_in_box.h (shared with csrc/part_head.hip).
 //
 // MI355X design: the boxes of a frame are staged once per workgroup in LDS together with their sin/cos (the reference
 // recomputes sin/cos for every point x box pair); the pool's per-box point collection runs one WAVE per box over
 // 64-point chunks with ballot-ranked ordered appends instead of one serial thread per box.
 #include "crb_common.h"
+#include "pt_in_box.h"
 #include "../../include/crb_hip.h"
 
 namespace {
-
-struct BoxLds { float cx, cy, cz, dx, dy, dz, ca, sa; };
-
-__device__ __forceinline__ bool pt_in_box(float x, float y, float z, const BoxLds& b, float& lx, float& ly) {
-  if ((double)fabsf(z - b.cz) > (double)b.dz / 2.0) return false;
-  const float sx = x - b.cx, sy = y - b.cy;
-  lx = sx * b.ca + sy * (-b.sa);
-  ly = sx * b.sa + sy * b.ca;
-  const double margin = (double)1e-5f;
-  return ((double)fabsf(lx) < (double)b.dx / 2.0 + margin) && ((double)fabsf(ly) < (double)b.dy / 2.0 + margin);
-}
-
-__device__ __forceinline__ BoxLds load_box(const float* p) {
-  BoxLds b;
-  b.cx = p[0]; b.cy = p[1]; b.cz = p[2]; b.dx = p[3]; b.dy = p[4]; b.dz = p[5];
-  b.ca = cosf(-p[6]); b.sa = sinf(-p[6]);
-  return b;
-}
 
 constexpr int PIB_CHUNK = 256;
 

@@ -62,7 +62,11 @@ class _Backbone8xBase(nn.Module):
         return batch_dict
 
     def _chain(self):
-        return [self.conv_input, self.conv1, self.conv2, self.conv3, self.conv4, self.conv_out]
+        return [m for m in (self.conv_input, self.conv1, self.conv2, self.conv3, self.conv4, self.conv_out) if m is not None]
+
+    def _decode(self, batch_dict, feats):
+        """what a subclass runs on the four encoder levels inside the same pass (UNetV2's decoder): its layers find their rulebooks
+        in the encoder's indice_dict and their weight layouts among the ones prepared for this step"""
 
     def _input_tensor(self, batch_dict):
         voxel_features, voxel_coords = batch_dict['voxel_features'], batch_dict['voxel_coords']
@@ -113,7 +117,8 @@ class _Backbone8xBase(nn.Module):
         x2 = self.conv2(x1)
         x3 = self.conv3(x2)
         x4 = self.conv4(x3)
-        out = self.conv_out(x4)
+        out = self.conv_out(x4) if self.conv_out is not None else None
+        self._decode(batch_dict, (x1, x2, x3, x4))
         if torch.is_grad_enabled() and x.features.is_cuda:
             from crbhip import sparse as _sp
             _sp._PREP_W.clear()          # the forward operands were for THIS pass (the backward finds its operands by their own address)

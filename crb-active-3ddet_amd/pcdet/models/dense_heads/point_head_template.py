@@ -99,6 +99,8 @@ class PointHeadTemplate(nn.Module):
         SPC keypoints) says otherwise; gt_boxes (B,M,8)
         -> point_cls_labels (N) long: class (or 1) inside a gt box, -1 in the enlarged shell only, 0 elsewhere"""
         assert points.dim() == 2 and points.shape[1] == 4 and gt_boxes.dim() == 3 and gt_boxes.shape[2] == 8
+        if ret_part_labels:
+            return self.assign_part_targets(points, gt_boxes, ret_box_labels, set_ignore_flag, use_ball_constraint)
         assert set_ignore_flag and not use_ball_constraint and not ret_box_labels and not ret_part_labels, \
             'only the PointHeadSimple target mode is on the hot path'
         B = gt_boxes.shape[0]
@@ -144,6 +146,33 @@ class PointHeadTemplate(nn.Module):
             fg_val = gt_boxes[bs, inner.clamp(min=0), -1].long()
         labels = torch.where(fg, fg_val, labels)
         return {'point_cls_labels': labels, 'point_box_labels': None, 'point_part_labels': None}
+
+    def assign_part_targets(self, points, gt_boxes, ret_box_labels=False, set_ignore_flag=True, use_ball_constraint=False):
+        """the part-label mode of assign_stack_targets (Part-A2: ret_part_labels=True, set_ignore_flag): frames of any size, all in one
+        launch on device tensors (csrc/part_head.hip), the batched torch expressions on host tensors or with FUSED off
+        -> point_cls_labels (N) long, point_part_labels (N,3): rotate_z(p - c, -rz) / dims + 0.5 inside the owning box, zeros elsewhere"""
+        from crbhip import part_head
+        assert set_ignore_flag and not use_ball_constraint and not ret_box_labels, \
+            'part labels: only the set_ignore_flag mode without box labels (PartA2.yaml) is built'
+        extra = self.model_cfg.TARGET_CONFIG.GT_EXTRA_WIDTH
+        route = part_head.part_targets if FUSED else part_head.part_targets_torch
+        labels, part, _ = route(points.detach(), gt_boxes.detach(), extra, self.num_class)
+        return {'point_cls_labels': labels, 'point_box_labels': None, 'point_part_labels': part}
+
+    def get_part_head_loss(self, tb_dict=None):
+        """get_cls_layer_loss + get_part_layer_loss of the reference (point_head_template.py:131-173) as one pair of launches; the
+        torch expressions on host tensors or with FUSED off -> point_loss_cls + point_loss_part"""
+        from crbhip import part_head
+        ret = self.forward_ret_dict
+        labels = ret['point_cls_labels'].view(-1)
+        cls_preds = ret['point_cls_preds'].view(-1, self.num_class)
+        weights = self.model_cfg.LOSS_CONFIG.LOSS_WEIGHTS
+        args = (cls_preds, ret['point_part_preds'], labels, ret['point_part_labels'], float(self.cls_loss_func.alpha),
+                float(self.cls_loss_func.gamma), float(weights['point_cls_weight']), float(weights['point_part_weight']))
+        loss_cls, loss_part, pos = (part_head.part_loss if FUSED else part_head.part_loss_torch)(*args)
+        tb_dict = {} if tb_dict is None else tb_dict
+        tb_dict.update({'point_loss_cls': loss_cls.detach(), 'point_loss_part': loss_part.detach(), 'point_pos_num': pos.detach()})
+        return loss_cls + loss_part, tb_dict
 
     def get_cls_layer_loss(self, tb_dict=None, reduce=True):
         labels = self.forward_ret_dict['point_cls_labels'].view(-1)

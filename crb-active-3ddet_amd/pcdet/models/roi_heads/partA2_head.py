@@ -4,8 +4,9 @@ sparse tensor (batch index = RoI), dense flatten, shared FC, class / box branche
 
 Everything numeric runs on the HIP entry points the other heads already use: crb_roiaware_pool3d_forward / _backward
 (RoIAwarePool3d), the subm rulebook + gather-GEMM of the spconv mirror (4->64, 64->64, C_in->64), crb_sparse_to_dense.
-The detector around it in the reference (UNetV2 + PointIntraPartOffsetHead, part_a2_net.py) is out of scope (SURVEY §2.1
-row 8); the head consumes `point_part_offset` / `point_cls_scores` / `point_features` from whichever point head fills them."""
+What it consumes is in the tree: `point_features` / `point_coords` at the voxel centres from UNetV2 (backbones_3d/spconv_unet.py),
+`point_part_offset` / `point_cls_scores` from PointIntraPartOffsetHead (dense_heads/point_intra_part_head.py). The detector class that
+chains them (part_a2_net.py) and its configuration are not built yet."""
 import torch
 import torch.nn as nn
 

@@ -764,6 +764,35 @@ int crb_point_focal_loss_per_frame(const float* preds, const int64_t* labels, in
                                    float loss_weight, float* loss, float* d_preds, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * point head of Part-A2 in training (csrc/part_head.hip)
+ * crb_part_targets replaces PointHeadTemplate.assign_stack_targets in set_ignore_flag mode with ret_part_labels=True
+ *   (pcdet/models/dense_heads/point_head_template.py:49-129: a loop over the frames with a host sync each) for all frames in one launch:
+ *   points (N,4) f32 [b,x,y,z] frame-sorted, frame_offsets (B+1) i32 on the device (frames may differ in size or be empty), gt_boxes
+ *   (B,G,8) zero padded, class last; extra_width: 3 HOST floats (TARGET_CONFIG.GT_EXTRA_WIDTH), added to the dims as
+ *   box_utils.enlarge_box3d does -> labels (N) i64: the class of the first ground truth in index order that contains the point (1 when
+ *   num_class == 1), -1 where only an enlarged ground truth does, 0 elsewhere; part_labels (N,3) f32 = rotate_z(p - c, -rz) / dims + 0.5
+ *   of an owned point (formed in f64, rounded once), zeros elsewhere; owner (N) i32 = that ground truth's index or -1.
+ *   Containment is the test of crb_points_in_boxes (csrc/pt_in_box.h): labels equal the crb_points_in_boxes + crb_point_labels route bit
+ *   for bit. The ground truths are staged in LDS 64 at a time: any G.
+ * crb_part_loss_forward replaces get_cls_layer_loss (:131-158) + get_part_layer_loss (:160-173) and their autograd: cls_preds (n,C)
+ *   logits, part_preds (n,3) logits, labels (n) i64, part_labels (n,3) -> loss (3) f64 = {point_loss_cls = cls_weight * sum of the focal
+ *   terms of the rows with label >= 0 / max(pos,1), point_loss_part = part_weight * sum of the binary cross entropies
+ *   max(x,0) - x t + log1p(exp(-|x|)) of the rows with label > 0 / (3 max(pos,1)), pos}; d_cls (n,C), d_part (n,3) = the gradients of the
+ *   two losses for unit upstream values. Two launches over cdiv(n,1024) workgroups: f32 terms, f64 sums inside a workgroup and across
+ *   workgroups in a fixed order, no atomics - bit-identical from call to call. workspace: crb_part_loss_workspace_bytes(n), uninitialised.
+ * crb_part_loss_backward: grad_losses (2) f32 on the device = upstream gradients of the two losses -> grad_cls = d_cls * grad_losses[0],
+ *   grad_part = d_part * grad_losses[1]. One launch, no host read-back.
+ * ---------------------------------------------------------------------------------------------- */
+int crb_part_targets(const float* points, const int32_t* frame_offsets, const float* gt_boxes, int B, int64_t N, int G,
+                     const float* extra_width, int num_class, int64_t* labels, float* part_labels, int32_t* owner, void* stream);
+int64_t crb_part_loss_workspace_bytes(int64_t n);
+int crb_part_loss_forward(const float* cls_preds, const float* part_preds, const int64_t* labels, const float* part_labels, int64_t n,
+                          int C, float alpha, float gamma, float cls_weight, float part_weight, double* loss, float* d_cls, float* d_part,
+                          void* workspace, int64_t workspace_bytes, void* stream);
+int crb_part_loss_backward(const float* d_cls, const float* d_part, const float* grad_losses, int64_t n, int C, float* grad_cls,
+                           float* grad_part, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * a22 / a24  second-stage losses and the canonical transformation of the sampled ground truths (csrc/rcnn_loss.hip)
  * replaces: RoIHeadTemplate.get_box_cls_layer_loss (BinaryCrossEntropy; pcdet/models/roi_heads/roi_head_template.py:261-285),
  *           get_box_reg_layer_loss (smooth-l1 + CORNER_LOSS_REGULARIZATION, the branch without reg_sample_targets; :142-259) with
