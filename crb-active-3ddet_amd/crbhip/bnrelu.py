@@ -340,15 +340,71 @@ class _BNReLUConcatTrain(torch.autograd.Function):
     def backward(ctx, dz):
         if dz is None:                            # the map's only consumer returned no gradient for it: nothing to launch
             return (None,) * (1 + 7 * len(ctx.widths))
-        dz = dz.contiguous().float()
-        saved = ctx.saved_tensors
-        grads, col = [None], 0
-        for i, C in enumerate(ctx.widths):
-            x, mean, invstd, g, b = saved[5 * i:5 * i + 5]
-            dx, dgamma, dbeta = concat_backward(x, dz, col, mean, invstd, g, b, ctx.relu)
-            grads += [dx, dgamma, dbeta, None, None, None, None]
-            col += C
+        grads = [None]
+        for g in _concat_grads(ctx, dz):
+            grads += list(g) + [None, None, None, None]
         return tuple(grads)
+
+
+def _concat_grads(ctx, dz):
+    """[(dx, dgamma, dbeta)] per branch of a concatenated map with gradient dz, from what its forward saved"""
+    dz = dz.contiguous().float()
+    saved = ctx.saved_tensors
+    grads, col = [], 0
+    for i, C in enumerate(ctx.widths):
+        x, mean, invstd, g, b = saved[5 * i:5 * i + 5]
+        grads.append(concat_backward(x, dz, col, mean, invstd, g, b, ctx.relu))
+        col += C
+    return grads
+
+
+def concat_apply(saved, relu=True):
+    """the concatenated map (n, sum C_i) from known statistics: one apply launch per branch, saved = [(x contiguous, mean, invstd,
+    gamma f32, beta f32)]; no autograd"""
+    import ctypes
+    n, dev = saved[0][0].shape[0], saved[0][0].device
+    widths = [s[0].shape[1] for s in saved]
+    total = sum(widths)
+    out = torch.empty((n, total), dtype=torch.float32, device=dev)
+    col = 0
+    for (x, mean, invstd, g, b), C in zip(saved, widths):
+        check(lib.crb_bn_relu_apply(ptr(x), n, C, ptr(mean), ptr(invstd), ptr(g), ptr(b), int(relu),
+                                    ctypes.c_void_p(out.data_ptr() + 4 * col), total, cur_stream(dev)), 'crb_bn_relu_apply')
+        col += C
+    return out
+
+
+class _BNReLUConcatApply(torch.autograd.Function):
+    """the map of `_BNReLUConcatTrain` from statistics that are already known (a deferred `bn_relu_concat`): the apply launches only,
+    the same kernel on the same numbers, and the same backward. Arguments: relu, the saved tensors [(x contiguous, mean, invstd,
+    gamma f32, beta f32)], then (x, gamma, beta) per branch - the tensors the gradients belong to."""
+
+    @staticmethod
+    def forward(ctx, relu, saved, *branch):
+        out = concat_apply(saved, relu)
+        widths = [s[0].shape[1] for s in saved]
+        ctx.save_for_backward(*[t for s in saved for t in s])
+        ctx.relu, ctx.widths = int(relu), widths
+        ctx.set_materialize_grads(False)
+        return out
+
+    @staticmethod
+    def backward(ctx, dz):
+        if dz is None:
+            return (None,) * (2 + 3 * len(ctx.widths))
+        grads = [None, None]
+        for g in _concat_grads(ctx, dz):
+            grads += list(g)
+        return tuple(grads)
+
+
+def materialize_concat(record):
+    """the map of a pending `head_bn.Record` (see `bn_relu_concat(defer=True)`), noted like the map of a call that was not deferred"""
+    from . import head_bn
+    out = _BNReLUConcatApply.apply(record.relu, record.saved, *[t for trio in record.inputs for t in trio])
+    if torch.is_grad_enabled():
+        out._crb_head_bn = head_bn.Record(out, record.inputs, record.saved, record.relu)
+    return out
 
 
 _CONCAT_SAVED = None       # what the last _BNReLUConcatTrain.forward saved, for the record bn_relu_concat notes on the map
@@ -377,9 +433,12 @@ def concat_reduce(x, dz, col, mean, invstd, g, b, relu=1):
     return dbeta, dgamma
 
 
-def bn_relu_concat(xs, bns, relu=True):
+def bn_relu_concat(xs, bns, relu=True, defer=False):
     """training-mode relu(bn_i(x_i)) for row matrices x_i (n, C_i), concatenated along the channel axis -> (n, sum C_i).
-    Every bn must be in training mode with a momentum (running statistics are updated in the forward launch)."""
+    Every bn must be in training mode with a momentum (running statistics are updated in the forward launch).
+    defer=True (grad mode on, no frame groups): the statistics launches only - the running statistics and the batch counters advance
+    as usual, once - and a pending `head_bn.Record` instead of the map: a linear head forms relu(bn(x)) itself
+    (`head_bn.linear_deferred`), anybody else calls `record.materialize()`."""
     if _GROUPS is not None and _GROUPS.G > 1:
         off = _GROUPS.offsets(xs[0])
         if not torch.is_grad_enabled():
@@ -392,6 +451,25 @@ def bn_relu_concat(xs, bns, relu=True):
             return out
         with frame_groups(1):
             return torch.cat([bn_relu_concat([x[a:b] for x in xs], bns, relu) for a, b in zip(off[:-1], off[1:])], 0)
+    if defer and torch.is_grad_enabled():
+        from . import head_bn
+        saved = []
+        with torch.no_grad():
+            for x, bn in zip(xs, bns):
+                bn.num_batches_tracked += 1
+                xc = x.detach().contiguous()
+                n, C = xc.shape
+                mean = torch.empty((C,), dtype=torch.float32, device=xc.device)
+                var, invstd = torch.empty_like(mean), torch.empty_like(mean)
+                wsb = lib.crb_bn_workspace_bytes(n, C)
+                ws, tk = _scratch(xc.device, wsb)
+                g, b = bn.weight.detach().contiguous().float(), bn.bias.detach().contiguous().float()
+                _bn_check(lib.crb_bn_relu_forward(ptr(xc), n, C, ptr(g), ptr(b), float(bn.eps), int(relu), None, 0, ptr(mean), ptr(var),
+                                                  ptr(invstd), ptr(bn.running_mean), ptr(bn.running_var), None, float(bn.momentum),
+                                                  ptr(ws), wsb, ptr(tk), cur_stream(xc.device)), 'crb_bn_relu_forward')
+                _touch(bn.running_mean, bn.running_var)
+                saved.append((xc, mean, invstd, g, b))
+        return head_bn.Record(None, [(x, bn.weight, bn.bias) for x, bn in zip(xs, bns)], saved, relu)
     args = []
     for x, bn in zip(xs, bns):
         with torch.no_grad():

@@ -23,6 +23,9 @@
 //      large sum is added ceil(K / 16) times. Epilogue: bn_bwd_apply_kernel's expression, in its order (-ffp-contract=off).
 // k past K is zero IN REGISTERS, rows past n count as zero / are not stored: their loads go to the last entries of the row / the last row of
 // the chunk instead (unconditional loads at clamped offsets from a uniform base), nothing is read past a row's end or past row n - 1.
+//
+// The forward of the same region, out = relu(bn(x)) W^T + b from the branch inputs without writing z, is head_bn_forward_kernel below
+// (its own comment): with it z does not exist in a training step.
 #include <atomic>
 #include <type_traits>
 #include <utility>
@@ -75,6 +78,41 @@ struct HbSplit8 {
     f[2] = __builtin_bit_cast(bf16x8, q2);
   }
 };
+
+// the forward kernel's accumulators: block B (16 registers) = a[16 B : 16 B + 15] by name (rows_gemm4.hip: as C++ values the register
+// allocator copies accumulator tuples around the MFMAs and spills). MFMA -> v_accvgpr_read needs wait states: hb_acc_settle()
+template <int B>
+__device__ __forceinline__ void hb_mfma_acc(const bf16x8& A, const bf16x8& Bv) {
+  asm volatile("v_mfma_f32_32x32x16_bf16 a[%2:%3], %0, %1, a[%2:%3]" : : "v"(A), "v"(Bv), "n"(B * 16), "n"(B * 16 + 15));
+}
+template <int R>
+__device__ __forceinline__ float hb_acc_read() {
+  float x;
+  asm volatile("v_accvgpr_read_b32 %0, a[%1]" : "=v"(x) : "n"(R));
+  return x;
+}
+template <int R>
+__device__ __forceinline__ void hb_acc_zero() { asm volatile("v_accvgpr_write_b32 a[%0], 0" : : "n"(R)); }
+__device__ __forceinline__ void hb_acc_settle() { asm volatile("s_nop 15\n\ts_nop 15" ::: "memory"); }
+
+#define HB_ACC_0_127                                                                                                                   \
+  "a0", "a1", "a2", "a3", "a4", "a5", "a6", "a7", "a8", "a9", "a10", "a11", "a12", "a13", "a14", "a15", "a16", "a17", "a18", "a19",   \
+      "a20", "a21", "a22", "a23", "a24", "a25", "a26", "a27", "a28", "a29", "a30", "a31", "a32", "a33", "a34", "a35", "a36", "a37",   \
+      "a38", "a39", "a40", "a41", "a42", "a43", "a44", "a45", "a46", "a47", "a48", "a49", "a50", "a51", "a52", "a53", "a54", "a55",   \
+      "a56", "a57", "a58", "a59", "a60", "a61", "a62", "a63", "a64", "a65", "a66", "a67", "a68", "a69", "a70", "a71", "a72", "a73",   \
+      "a74", "a75", "a76", "a77", "a78", "a79", "a80", "a81", "a82", "a83", "a84", "a85", "a86", "a87", "a88", "a89", "a90", "a91",   \
+      "a92", "a93", "a94", "a95", "a96", "a97", "a98", "a99", "a100", "a101", "a102", "a103", "a104", "a105", "a106", "a107", "a108", \
+      "a109", "a110", "a111", "a112", "a113", "a114", "a115", "a116", "a117", "a118", "a119", "a120", "a121", "a122", "a123", "a124", \
+      "a125", "a126", "a127"
+#define HB_ACC_128_255                                                                                                                 \
+  "a128", "a129", "a130", "a131", "a132", "a133", "a134", "a135", "a136", "a137", "a138", "a139", "a140", "a141", "a142", "a143",     \
+      "a144", "a145", "a146", "a147", "a148", "a149", "a150", "a151", "a152", "a153", "a154", "a155", "a156", "a157", "a158", "a159", \
+      "a160", "a161", "a162", "a163", "a164", "a165", "a166", "a167", "a168", "a169", "a170", "a171", "a172", "a173", "a174", "a175", \
+      "a176", "a177", "a178", "a179", "a180", "a181", "a182", "a183", "a184", "a185", "a186", "a187", "a188", "a189", "a190", "a191", \
+      "a192", "a193", "a194", "a195", "a196", "a197", "a198", "a199", "a200", "a201", "a202", "a203", "a204", "a205", "a206", "a207", \
+      "a208", "a209", "a210", "a211", "a212", "a213", "a214", "a215", "a216", "a217", "a218", "a219", "a220", "a221", "a222", "a223", \
+      "a224", "a225", "a226", "a227", "a228", "a229", "a230", "a231", "a232", "a233", "a234", "a235", "a236", "a237", "a238", "a239", \
+      "a240", "a241", "a242", "a243", "a244", "a245", "a246", "a247", "a248", "a249", "a250", "a251", "a252", "a253", "a254", "a255"
 
 // ------------------------------------------------------------------------------------------------------------------------------
 // par (4, Ct): mean | invstd | gamma | beta of the concatenated channels
@@ -413,6 +451,212 @@ __global__ __launch_bounds__(HB_NT, 2) void head_bn_apply_kernel(HaArgs a) {
   }
 }
 
+// ------------------------------------------------------------------------------------------------------------------------------
+// Forward of the same region without the map: out[r][k] = sum_c relu(gamma_c ((x[r][c] - mean_c) invstd_c) + beta_c) W[k][c] + b[k].
+// The structure of rows_gemm4_kernel's forward: computed transposed, D[k][row], so a lane ends with 4 consecutive outputs of ITS row
+// (16-byte stores); lane (r, h) loads 64 contiguous bytes of its row per 32 channels and uses them for two MFMA k steps (k step 2 c + u
+// holds channel 32 c + 16 h + 8 u + j for lane half h, element j); the activation is bn_apply_kernel's expression in its order on the
+// loaded values (a NaN stays a NaN where that kernel's comparison writes 0: a bad row shows in the head's outputs), the per-channel
+// constants of the 32 channels come from an LDS copy of par; the weight fragments are 16-byte loads from the lane-order image
+// [K block][k step Ct / 16][piece 3][lane 64][8 bf16] (lane (r, h), element j: W[32 kb + r][channel], zero past K) straight from L2.
+// Persistent workgroups of 4 waves, one per SIMD, wave tile 64 rows x all K; one loop over (tile, 32 channels) that requests the next
+// step's rows and fragments ahead of this step's MFMAs. Two accumulator sets (the leading pass | the five small ones) added in the
+// epilogue with the bias. No atomics, fixed order.
+constexpr int HF_TILE = 256;              // rows per workgroup tile
+
+struct HfArgs {
+  const float* x0;
+  const float* x1;
+  const float* par;           // (4, Ct)
+  const unsigned char* wimg;
+  const float* bias;          // (K)
+  float* out;                 // (n, K)
+  int64_t n, tiles;
+  int C, Ct, K;
+};
+
+__global__ __launch_bounds__(256) void head_bn_forward_weights_kernel(const float* __restrict__ w, unsigned char* __restrict__ img, int K,
+                                                                      int Ct, int NKB) {
+  const int KS = Ct >> 4;
+  const int id = blockIdx.x * 256 + threadIdx.x;         // (kb, k step, lane)
+  if (id >= NKB * KS * 64) return;
+  const int lane = id & 63, r = lane & 31, h = lane >> 5;
+  const int ks = (id >> 6) % KS, kb = (id >> 6) / KS;
+  const int k = 32 * kb + r, c0 = (ks >> 1) * 32 + h * 16 + (ks & 1) * 8;
+  u32x4 q[3];
+  unsigned lo[3] = {0, 0, 0};
+#pragma unroll
+  for (int j = 0; j < 8; ++j) {
+    const float v = k < K ? w[(int64_t)k * Ct + c0 + j] : 0.f;
+    unsigned p[3];
+    split3(v, p[0], p[1], p[2]);
+#pragma unroll
+    for (int i = 0; i < 3; ++i) {
+      if (j & 1) q[i][j >> 1] = lo[i] | (p[i] << 16);
+      else lo[i] = p[i];
+    }
+  }
+  unsigned char* dst = img + ((int64_t)(kb * KS + ks) * 3) * 1024 + lane * 16;
+#pragma unroll
+  for (int i = 0; i < 3; ++i) *reinterpret_cast<u32x4*>(dst + i * 1024) = q[i];
+}
+
+template <int NKB>
+__global__ __launch_bounds__(HB_NT, 1) void head_bn_forward_kernel(HfArgs a) {
+  __shared__ __attribute__((aligned(16))) float cst[4 * 512];      // par: mean | invstd | gamma | beta, (4, Ct)
+  asm volatile("" ::: HB_ACC_0_127, HB_ACC_128_255);
+  for (int i = threadIdx.x; i < 4 * a.Ct; i += HB_NT) cst[i] = a.par[i];
+  __syncthreads();
+  const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const int r = lane & 31, h = lane >> 5;
+  const int KC = a.Ct >> 5, KS = a.Ct >> 4;
+  int64_t lt = blockIdx.x;
+  int lc = 0;
+  if (lt >= a.tiles) return;
+  const unsigned char* const wl = a.wimg + lane * 16;
+
+  int64_t xoff[2];            // the lane's rows of the tile the loads belong to (rows past n: the last row), as element offsets
+  auto set_rows = [&](int64_t tile) __attribute__((always_inline)) {
+#pragma unroll
+    for (int rb = 0; rb < 2; ++rb) {
+      const int64_t m = tile * HF_TILE + wave * 64 + rb * 32 + r;
+      xoff[rb] = (m < a.n ? m : a.n - 1) * a.C;
+    }
+  };
+  // the lane's 64 bytes of 32 channels as two halves: `hi` = 0 the 8 values of k step 2 c, 1 those of k step 2 c + 1
+  auto load_a = [&](int c, int hi, hb_f32x4 (&dst)[2][2]) __attribute__((always_inline)) {
+    const int branch = (32 * c) / a.C;
+    const float* const xb = (branch ? a.x1 : a.x0) + (32 * c - branch * a.C + 16 * h + 8 * hi);
+#pragma unroll
+    for (int rb = 0; rb < 2; ++rb)
+#pragma unroll
+      for (int q = 0; q < 2; ++q) dst[rb][q] = *reinterpret_cast<const hb_f32x4*>(xb + xoff[rb] + 4 * q);
+  };
+  auto load_b = [&](int ks, bf16x8 (&dst)[NKB][3]) __attribute__((always_inline)) {
+#pragma unroll
+    for (int kb = 0; kb < NKB; ++kb)
+#pragma unroll
+      for (int p = 0; p < 3; ++p) dst[kb][p] = *reinterpret_cast<const bf16x8*>(wl + ((size_t)(kb * KS + ks) * 3 + p) * 1024);
+  };
+  // the constants of the 8 channels 32 c + 16 h + 8 u + (0 .. 7): [q][mean | invstd | gamma | beta]
+  auto load_c = [&](int c, int u, hb_f32x4 (&dst)[2][4]) __attribute__((always_inline)) {
+    const float* const cp = cst + 32 * c + 16 * h + 8 * u;
+#pragma unroll
+    for (int q = 0; q < 2; ++q)
+#pragma unroll
+      for (int p = 0; p < 4; ++p) dst[q][p] = *reinterpret_cast<const hb_f32x4*>(cp + p * a.Ct + 4 * q);
+  };
+  // value e of 8: bn_apply_kernel's expression in its order, four values at a time (a NaN stays a NaN), then its three pieces
+  hb_f32x4 act;
+  auto value = [&](auto ec, HbSplit8& sp, const hb_f32x4 (&v)[2], const hb_f32x4 (&cs)[2][4]) __attribute__((always_inline)) {
+    constexpr int e = decltype(ec)::value, q = e >> 2;
+    if constexpr ((e & 3) == 0) act = cs[q][2] * ((v[q] - cs[q][0]) * cs[q][1]) + cs[q][3];
+    sp.put<e>(act[e & 3] <= 0.f ? 0.f : act[e & 3]);
+  };
+  // D[k][row] += W fragment (first operand, K block kb) . activation fragment (second operand, row block rb): the pass of the two leading
+  // pieces into accumulator block rb NKB + kb, the five passes below 2^-8 of it into block 2 NKB + rb NKB + kb (rows_gemm4.hip)
+  auto step = [&](const bf16x8 (&Bw)[NKB][3], const bf16x8 (&Xf)[2][3], auto&& gap) __attribute__((always_inline)) {
+    hb_static_for<12 * NKB>([&](auto kc) __attribute__((always_inline)) {
+      constexpr int k = decltype(kc)::value, rb = k / (6 * NKB), kb = (k / 6) % NKB, pass = k % 6;
+      hb_mfma_acc<(pass == 5 ? 0 : 2 * NKB) + rb * NKB + kb>(Bw[kb][hb_pass_a(pass)], Xf[rb][hb_pass_b(pass)]);
+      gap(kc);
+      __builtin_amdgcn_sched_barrier(0);
+    });
+  };
+
+  hb_static_for<64 * NKB>([](auto rc) { hb_acc_zero<decltype(rc)::value>(); });
+  hb_f32x4 Ahi[2][2], CS1[2][4];
+  bf16x8 XF0[2][3], B0[NKB][3];
+  set_rows(lt);
+  {
+    hb_f32x4 A0[2][2], CS0[2][4];
+    load_a(0, 0, A0);
+    load_a(0, 1, Ahi);
+    load_b(0, B0);
+    load_c(0, 0, CS0);
+    load_c(0, 1, CS1);
+#pragma unroll
+    for (int rb = 0; rb < 2; ++rb) {
+      HbSplit8 sp;
+      hb_static_for<8>([&](auto ec) __attribute__((always_inline)) { value(ec, sp, A0[rb], CS0); });
+      sp.get(XF0[rb]);
+    }
+  }
+  asm volatile("s_nop 4" ::: "memory");
+
+  for (;;) {
+    int64_t nt = lt;
+    int nc = lc + 1;
+    if (nc == KC) { nc = 0; nt = lt + gridDim.x; }
+    const bool more = nt < a.tiles;
+    if (!more) { nt = lt; nc = lc; }            // (the last step of the loop requests its own operands again; nobody uses them)
+    bf16x8 B1[NKB][3];
+    load_b(2 * lc + 1, B1);
+    if (nt != lt) set_rows(nt);
+    hb_f32x4 An[2][2], CS0n[2][4];
+    load_a(nc, 0, An);
+    load_c(nc, 0, CS0n);
+    __builtin_amdgcn_sched_barrier(0);
+
+    // k step 0 of these 32 channels; in its gaps the activation and split of k step 1
+    bf16x8 XF1[2][3];
+    HbSplit8 sp;
+    step(B0, XF0, [&](auto kc) __attribute__((always_inline)) {
+      constexpr int k = decltype(kc)::value;
+      if constexpr (k < 16) {
+        constexpr int rb = k >> 3, e = k & 7;
+        value(std::integral_constant<int, e>{}, sp, Ahi[rb], CS1);
+        if constexpr (e == 7) sp.get(XF1[rb]);
+      }
+    });
+    load_b(2 * nc, B0);
+    load_a(nc, 1, Ahi);       // (the other half of the 64 bytes whose first half is already requested)
+    load_c(nc, 1, CS1);
+    __builtin_amdgcn_sched_barrier(0);
+    // k step 1; in its gaps the activation and split of k step 0 of the next 32 channels
+    bf16x8 XF0n[2][3];
+    step(B1, XF1, [&](auto kc) __attribute__((always_inline)) {
+      constexpr int k = decltype(kc)::value;
+      if constexpr (k >= 8 && k < 24) {
+        constexpr int rb = (k - 8) >> 3, e = (k - 8) & 7;
+        value(std::integral_constant<int, e>{}, sp, An[rb], CS0n);
+        if constexpr (e == 7) sp.get(XF0n[rb]);
+      }
+    });
+
+    if (lc == KC - 1) {
+      // ---- the tile is complete: accumulator register 4 j + e of block (rb, kb) = row 32 rb + r, output 32 kb + 8 j + 4 h + e
+      hb_acc_settle();
+      hb_static_for<2>([&](auto rbc) __attribute__((always_inline)) {
+        constexpr int rb = decltype(rbc)::value;
+        const int64_t m = lt * HF_TILE + wave * 64 + rb * 32 + r;
+        const bool ok = m < a.n;
+        float* const out = a.out + (ok ? m : a.n - 1) * a.K + 4 * h;
+        hb_static_for<4 * NKB>([&](auto qc) __attribute__((always_inline)) {
+          constexpr int kb = decltype(qc)::value >> 2, j = decltype(qc)::value & 3;
+          constexpr int R0 = (rb * NKB + kb) * 16 + 4 * j, R1 = R0 + 2 * NKB * 16;
+          const int k0 = 32 * kb + 8 * j + 4 * h;
+          const hb_f32x4 v = (hb_f32x4){hb_acc_read<R0>() + hb_acc_read<R1>(), hb_acc_read<R0 + 1>() + hb_acc_read<R1 + 1>(),
+                                        hb_acc_read<R0 + 2>() + hb_acc_read<R1 + 2>(), hb_acc_read<R0 + 3>() + hb_acc_read<R1 + 3>()};
+          if (k0 < a.K) {                                   // K is a multiple of 4: a quad is inside or outside
+            const hb_f32x4 b = (hb_f32x4){a.bias[k0], a.bias[k0 + 1], a.bias[k0 + 2], a.bias[k0 + 3]};
+            if (ok) *reinterpret_cast<hb_f32x4*>(out + 32 * kb + 8 * j) = v + b;
+          }
+        });
+      });
+      hb_static_for<64 * NKB>([](auto rc) { hb_acc_zero<decltype(rc)::value>(); });
+      asm volatile("s_nop 4" ::: "memory");
+    }
+    if (!more) break;
+#pragma unroll
+    for (int rb = 0; rb < 2; ++rb)
+#pragma unroll
+      for (int p = 0; p < 3; ++p) XF0[rb][p] = XF0n[rb][p];
+    lt = nt;
+    lc = nc;
+  }
+}
+
 __host__ int hb_cu_count() {
   static std::atomic<int> n_cu{0};
   int n = n_cu.load(std::memory_order_relaxed);
@@ -515,6 +759,38 @@ extern "C" int crb_head_bn_apply(const float* x0, const float* x1, const float* 
   const dim3 grid((unsigned)(groups * a.ncg));
   if (K > 64) hipLaunchKernelGGL(head_bn_apply_kernel<5>, grid, dim3(HB_NT), 0, (hipStream_t)stream, a);
   else hipLaunchKernelGGL(head_bn_apply_kernel<4>, grid, dim3(HB_NT), 0, (hipStream_t)stream, a);
+  CRB_CHECK_LAUNCH();
+  return CRB_OK;
+}
+
+extern "C" int64_t crb_bn_head_forward_weights_bytes(int nbranch, int width, int K) {
+  if (!crb_head_bn_supported(nbranch, width, K)) return 0;
+  return (int64_t)((K + 31) / 32) * (nbranch * width / 16) * 3 * 1024;
+}
+
+extern "C" int crb_bn_head_forward_weights(const float* w, void* image, int nbranch, int width, int K, void* stream) {
+  if (!crb_head_bn_supported(nbranch, width, K)) return CRB_ERR_UNSUPPORTED;
+  if (!w || !image) return CRB_ERR_ARG;
+  const int Ct = nbranch * width, NKB = (K + 31) / 32;
+  const int threads = NKB * (Ct / 16) * 64;
+  hipLaunchKernelGGL(head_bn_forward_weights_kernel, dim3((unsigned)crb_cdiv(threads, 256)), dim3(256), 0, (hipStream_t)stream, w,
+                     (unsigned char*)image, K, Ct, NKB);
+  CRB_CHECK_LAUNCH();
+  return CRB_OK;
+}
+
+extern "C" int crb_bn_head_forward(const float* x0, const float* x1, const float* par, const void* image, const float* bias, int64_t n,
+                                   int nbranch, int width, int K, float* out, void* stream) {
+  if (!crb_head_bn_supported(nbranch, width, K)) return CRB_ERR_UNSUPPORTED;
+  if (n <= 0 || n >= (1LL << 34) || !x0 || !x1 || !par || !image || !bias || !out) return CRB_ERR_ARG;
+  HfArgs a;
+  a.x0 = x0; a.x1 = x1; a.par = par; a.wimg = (const unsigned char*)image; a.bias = bias; a.out = out;
+  a.n = n; a.tiles = (n + HF_TILE - 1) / HF_TILE;
+  a.C = width; a.Ct = nbranch * width; a.K = K;
+  const int cus = hb_cu_count();
+  const dim3 grid((unsigned)(a.tiles < cus ? a.tiles : cus));
+  if (K > 64) hipLaunchKernelGGL(head_bn_forward_kernel<3>, grid, dim3(HB_NT), 0, (hipStream_t)stream, a);
+  else hipLaunchKernelGGL(head_bn_forward_kernel<2>, grid, dim3(HB_NT), 0, (hipStream_t)stream, a);
   CRB_CHECK_LAUNCH();
   return CRB_OK;
 }

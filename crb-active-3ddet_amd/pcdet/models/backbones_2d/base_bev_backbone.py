@@ -77,6 +77,9 @@ class BaseBEVBackbone(nn.Module):
                 nn.ConvTranspose2d(c_in, c_in, upsample_strides[-1], stride=upsample_strides[-1], bias=False),
                 _bn(c_in), nn.ReLU()))
         self.num_bev_features = c_in
+        # set by a detector whose anchor head is the concatenated map's only reader: the training path hands the head a pending
+        # crbhip.head_bn.Record under 'spatial_features_2d_pending' instead of writing the map
+        self.defer_concat = False
 
     @staticmethod
     def _run_folded(seq, x):
@@ -296,7 +299,16 @@ class BaseBEVBackbone(nn.Module):
                             for p in pre):
             n, _, h, w_ = pre[0].shape
             rows = [p.permute(0, 2, 3, 1).reshape(n * h * w_, p.shape[1]) for p in pre]
-            cat = bnrelu.bn_relu_concat(rows, [d[1] for d in self.deblocks[:len(pre)]], relu=True)
+            defer = self.defer_concat and torch.is_grad_enabled() and not bnrelu.frame_groups_active()
+            cat = bnrelu.bn_relu_concat(rows, [d[1] for d in self.deblocks[:len(pre)]], relu=True, defer=defer)
+            if defer:
+                # the head is the map's only reader and forms relu(bn(x)) itself (crbhip.head_bn.linear_deferred): the map is not
+                # written, and the key a reader would look for is not set
+                cat.nhw = (n, h, w_)
+                data_dict['spatial_features_2d_pending'] = cat
+                from crbhip import winograd
+                winograd.forget_prepared_forward()
+                return data_dict
             ups = [cat.view(n, h, w_, cat.shape[1]).permute(0, 3, 1, 2)]
             if len(self.deblocks) == len(self.blocks) and getattr(cat, '_crb_head_bn', None) is not None:
                 ups[0]._crb_head_bn = cat._crb_head_bn         # for a linear head on this map (crbhip.head_bn)

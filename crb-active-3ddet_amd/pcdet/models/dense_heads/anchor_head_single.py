@@ -32,8 +32,21 @@ class AnchorHeadSingle(AnchorHeadTemplate):
         nn.init.constant_(self.conv_cls.bias, -np.log((1 - pi) / pi))
         nn.init.normal_(self.conv_box.weight, mean=0, std=0.001)
 
+    @staticmethod
+    def _feats(data_dict):
+        """the backbone's map; a record the backbone left pending (BaseBEVBackbone.defer_concat) is written first and takes the key
+        the map has"""
+        record = data_dict.pop('spatial_features_2d_pending', None)
+        if record is not None:
+            n, h, w_ = record.nhw
+            rows = record.materialize()
+            feats = rows.view(n, h, w_, rows.shape[1]).permute(0, 3, 1, 2)
+            if getattr(rows, '_crb_head_bn', None) is not None:
+                feats._crb_head_bn = rows._crb_head_bn
+            data_dict['spatial_features_2d'] = feats
+        return data_dict['spatial_features_2d']
+
     def forward(self, data_dict):
-        feats = data_dict['spatial_features_2d']
         if FUSED_HEAD_CONVS:
             # the three 1x1 convs (anchor_head_single.py:57-72) read the same (B,512,H,W) map — 1.15 GB at KITTI bs=16:
             # as ONE convolution over the concatenated filters the map is read once instead of three times, and its
@@ -42,12 +55,21 @@ class AnchorHeadSingle(AnchorHeadTemplate):
             heads = [self.conv_cls, self.conv_box] + ([self.conv_dir_cls] if self.conv_dir_cls is not None else [])
             w = torch.cat([h.weight for h in heads], 0)
             b = torch.cat([h.bias for h in heads], 0)
-            rows = rows_view(feats) if (ROWS_GEMM and feats.is_cuda) else None
+            y = None
+            pending = data_dict.get('spatial_features_2d_pending', None)
+            if pending is not None and ROWS_GEMM:
+                # the backbone did not write its concatenated BatchNorm + ReLU map: the head forms it in registers from the branch
+                # outputs and their statistics (None: no instance or switched off - the map is written below and read as before)
+                from crbhip import head_bn
+                y = head_bn.linear_deferred(pending, w.flatten(1), b)
+                if y is not None:
+                    y = y.view(pending.nhw + (w.shape[0],))
+            feats = self._feats(data_dict) if y is None else None
+            rows = rows_view(feats) if (y is None and ROWS_GEMM and feats.is_cuda) else None
             if rows is not None:
                 # channels_last: the 1x1 convolution is the GEMM (B*H*W, 512) x (512, sum C); its output rows already are the
                 # (B,H,W,sum C) layout the reference permutes to
                 n, _, h, w_ = feats.shape
-                y = None
                 record = getattr(feats, '_crb_head_bn', None)
                 if record is not None:
                     # the map is the concatenated BatchNorm + ReLU output of the backbone: the head's backward and that BatchNorm's
@@ -57,12 +79,13 @@ class AnchorHeadSingle(AnchorHeadTemplate):
                 if y is None:
                     y = LinearRows.apply(rows, w.flatten(1), b)
                 y = y.view(n, h, w_, w.shape[0])
-            else:
+            elif y is None:
                 y = torch.nn.functional.conv2d(feats, w, b).permute(0, 2, 3, 1)            # (B,H,W,sum C)
             outs = torch.split(y, [h.out_channels for h in heads], dim=3)
             cls_preds, box_preds = outs[0].contiguous(), outs[1].contiguous()
             dir_cls_preds = outs[2].contiguous() if self.conv_dir_cls is not None else None
         else:
+            feats = self._feats(data_dict)
             cls_preds = self.conv_cls(feats).permute(0, 2, 3, 1).contiguous()      # (B,H,W,C)
             box_preds = self.conv_box(feats).permute(0, 2, 3, 1).contiguous()
             dir_cls_preds = None

@@ -17,6 +17,7 @@ from ..model_utils import model_nms_utils
 
 
 LAZY_BOX_DECODE = True
+DEFER_CONCAT = True         # the BEV backbone's concatenated map is not written when an AnchorHeadSingle is its only reader
 
 
 class Detector3DTemplate(nn.Module):
@@ -170,6 +171,12 @@ class Detector3DTemplate(nn.Module):
             # two-stage detector: the RPN boxes are read by the RoI head's proposal layer only (its top-k), post-processing
             # reads the RoI head's own boxes — the dense head need not decode all anchors (LAZY_BOX_DECODE = False: it does)
             self.dense_head.lazy_box_decode = LAZY_BOX_DECODE
+        if hasattr(getattr(self, 'backbone_2d', None), 'defer_concat') and \
+                type(getattr(self, 'dense_head', None)) is dense_heads.AnchorHeadSingle and \
+                not any(getattr(m, 'reads_spatial_features_2d', False) for m in self.modules()):
+            # the anchor head is the only reader of the backbone's concatenated map: it takes the branch outputs and their BatchNorm
+            # statistics instead and the map is never written (crbhip.head_bn.linear_deferred)
+            self.backbone_2d.defer_concat = DEFER_CONCAT
         from ..backbones_2d.map_to_bev import height_compression
         if height_compression.CHANNELS_LAST:
             import torch as _torch

@@ -19,6 +19,8 @@ from .roi_head_template import RoIHeadTemplate
 
 
 class SECONDHead(RoIHeadTemplate):
+    reads_spatial_features_2d = True      # roi_grid_pool: the detector keeps the BEV backbone's concatenated map (no deferral)
+
     def __init__(self, input_channels, model_cfg, num_class=1, **kwargs):
         super().__init__(num_class=num_class, model_cfg=model_cfg)
         self.model_cfg = model_cfg

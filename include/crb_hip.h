@@ -1082,6 +1082,18 @@ int crb_head_bn_weights(const float* w, void* image, int nbranch, int width, int
 int crb_head_bn_apply(const float* x0, const float* x1, const float* par, const float* dgb, const float* dout, const void* image,
                       int64_t n, int nbranch, int width, int K, float* dx0, float* dx1, void* stream);
 
+/* Forward of the same region without the map (csrc/head_bn.hip): out (n, K) = relu(bn(x)) W^T + b from the branch inputs, with
+ * relu(bn(.)) = bn_apply_kernel's expression formed in registers (a NaN stays a NaN), the product through the exact three-way split
+ * (Inf -> NaN) with two accumulator sets. par as above (batch or running statistics). Same instances as crb_head_bn_supported.
+ * crb_bn_head_forward_weights: image (crb_bn_head_forward_weights_bytes) of W (K, Ct):
+ *   [ceil(K / 32)][Ct / 16][piece 3][lane 64][8 bf16], lane (r, h), element j of k step 2 c + u holds
+ *   W[32 kb + r][32 c + 16 h + 8 u + j], zero past K.
+ * crb_bn_head_forward: one launch of persistent workgroups; rows past n are not stored, nothing is read past row n - 1. */
+int64_t crb_bn_head_forward_weights_bytes(int nbranch, int width, int K);
+int crb_bn_head_forward_weights(const float* w, void* image, int nbranch, int width, int K, void* stream);
+int crb_bn_head_forward(const float* x0, const float* x1, const float* par, const void* image, const float* bias, int64_t n,
+                        int nbranch, int width, int K, float* out, void* stream);
+
 /* Scheduling hint, no reference counterpart: PV-RCNN's keypoint sampling (crb_furthest_point_sampling_stack on a side stream under
  * the backbones) holds one CU per frame for ~5 ms while the persistent one-workgroup-per-CU Winograd launches of the BEV backbone
  * run on the main stream. crb_cu_reservation(cus, stream) right before such a kernel, crb_cu_reservation(0, stream) right after it
