@@ -698,6 +698,14 @@ class SparseConvFunction(torch.autograd.Function):
 
 
 def sparse_conv(x, w_kio, rb, inverse=False, arithmetic='f32'):
+    cin, cout = w_kio.shape[1], w_kio.shape[2]
+    h = cout // 2
+    if x.is_cuda and not lib.crb_sparse_conv_supported(cin, cout) and cout % 2 == 0 and \
+            lib.crb_sparse_conv_supported(cin, h) and lib.crb_sparse_conv_supported(h, cin):
+        # a pair without a kernel instance whose output halves have one (16 -> 64: the Part-A2 RoI head on UNetV2's 16 point
+        # features): every output channel is its own sum of products, so the two halves side by side are the same numbers
+        return torch.cat([SparseConvFunction.apply(x, w_kio[:, :, :h], rb, inverse, arithmetic),
+                          SparseConvFunction.apply(x, w_kio[:, :, h:], rb, inverse, arithmetic)], dim=1)
     return SparseConvFunction.apply(x, w_kio, rb, inverse, arithmetic)
 
 

@@ -335,6 +335,62 @@ def pv_rcnn_plusplus_cfg(kind='kitti'):
     return c
 
 
+def parta2_net_cfg(kind='kitti'):
+    """values of tools/cfgs/kitti_models/PartA2.yaml; kind='waymo': tools/cfgs/waymo_models/PartA2.yaml (anchors, 4096 / 300 test
+    RoIs at 0.85, POOL_SIZE 10, final NMS 0.7). The yamls' anchors differ from the other models': every KITTI class sits at a bottom
+    height of -1.78."""
+    assert kind in ('kitti', 'waymo')
+    waymo = kind == 'waymo'
+    if waymo:
+        anchors = [_anchor('Vehicle', [4.7, 2.1, 1.7], 0, 0.55, 0.4), _anchor('Pedestrian', [0.91, 0.86, 1.73], 0, 0.5, 0.35),
+                   _anchor('Cyclist', [1.78, 0.84, 1.78], 0, 0.5, 0.35)]
+    else:
+        anchors = [_anchor('Car', [3.9, 1.6, 1.56], -1.78, 0.6, 0.45), _anchor('Pedestrian', [0.8, 0.6, 1.73], -1.78, 0.5, 0.35),
+                   _anchor('Cyclist', [1.76, 0.6, 1.73], -1.78, 0.5, 0.35)]
+    test_nms = {'NMS_TYPE': 'nms_gpu', 'MULTI_CLASSES_NMS': False, 'NMS_PRE_MAXSIZE': 4096 if waymo else 1024,
+                'NMS_POST_MAXSIZE': 300 if waymo else 100, 'NMS_THRESH': 0.85 if waymo else 0.7}
+    return EasyDict({
+        'CLASS_NAMES': ['Vehicle' if waymo else 'Car', 'Pedestrian', 'Cyclist'],
+        'DATA_CONFIG': {'DATASET': 'WaymoDataset' if waymo else 'KittiDataset'},
+        'MODEL': {
+            'NAME': 'PartA2Net',
+            'VFE': {'NAME': 'MeanVFE'},
+            'BACKBONE_3D': {'NAME': 'UNetV2'},
+            'MAP_TO_BEV': {'NAME': 'HeightCompression', 'NUM_BEV_FEATURES': 256},
+            'BACKBONE_2D': dict(_BEV),
+            'DENSE_HEAD': _dense_head(anchors),
+            'POINT_HEAD': {
+                'NAME': 'PointIntraPartOffsetHead', 'CLS_FC': [], 'PART_FC': [], 'CLASS_AGNOSTIC': True,
+                'TARGET_CONFIG': {'GT_EXTRA_WIDTH': [0.2, 0.2, 0.2]},
+                'LOSS_CONFIG': {'LOSS_REG': 'smooth-l1', 'LOSS_WEIGHTS': {'point_cls_weight': 1.0, 'point_part_weight': 1.0}}},
+            'ROI_HEAD': {
+                'NAME': 'PartA2FCHead', 'CLASS_AGNOSTIC': True, 'SHARED_FC': [256, 256, 256], 'CLS_FC': [256, 256],
+                'REG_FC': [256, 256], 'DP_RATIO': 0.3, 'SEG_MASK_SCORE_THRESH': 0.3,
+                'NMS_CONFIG': {
+                    'TRAIN': {'NMS_TYPE': 'nms_gpu', 'MULTI_CLASSES_NMS': False, 'NMS_PRE_MAXSIZE': 9000,
+                              'NMS_POST_MAXSIZE': 512, 'NMS_THRESH': 0.8},
+                    'TEST': test_nms},
+                'ROI_AWARE_POOL': {'POOL_SIZE': 10 if waymo else 12, 'NUM_FEATURES': 128, 'MAX_POINTS_PER_VOXEL': 128},
+                'TARGET_CONFIG': {'BOX_CODER': 'ResidualCoder', 'ROI_PER_IMAGE': 128, 'FG_RATIO': 0.5,
+                                  'SAMPLE_ROI_BY_EACH_CLASS': True, 'CLS_SCORE_TYPE': 'roi_iou', 'CLS_FG_THRESH': 0.75,
+                                  'CLS_BG_THRESH': 0.25, 'CLS_BG_THRESH_LO': 0.1, 'HARD_BG_RATIO': 0.8, 'REG_FG_THRESH': 0.65},
+                'LOSS_CONFIG': {'CLS_LOSS': 'BinaryCrossEntropy', 'REG_LOSS': 'smooth-l1', 'CORNER_LOSS_REGULARIZATION': True,
+                                'LOSS_WEIGHTS': {'rcnn_cls_weight': 1.0, 'rcnn_reg_weight': 1.0, 'rcnn_corner_weight': 1.0,
+                                                 'code_weights': [1.0, 1.0, 1.0, 1.0, 1.0, 1.0, 1.0]}}},
+            'POST_PROCESSING': {
+                'RECALL_THRESH_LIST': [0.3, 0.5, 0.7], 'SCORE_THRESH': 0.1, 'OUTPUT_RAW_SCORE': False,
+                'EVAL_METRIC': 'waymo' if waymo else 'kitti',
+                'NMS_CONFIG': {'MULTI_CLASSES_NMS': False, 'NMS_TYPE': 'nms_gpu', 'NMS_THRESH': 0.7 if waymo else 0.1,
+                               'NMS_PRE_MAXSIZE': 4096, 'NMS_POST_MAXSIZE': 500}},
+        },
+        'OPTIMIZATION': {'BATCH_SIZE_PER_GPU': 2 if waymo else 4, 'NUM_EPOCHS': 30 if waymo else 80, 'OPTIMIZER': 'adam_onecycle',
+                         'LR': 0.01, 'WEIGHT_DECAY': 0.01, 'MOMENTUM': 0.9, 'MOMS': [0.95, 0.85], 'PCT_START': 0.4,
+                         'DIV_FACTOR': 10, 'DECAY_STEP_LIST': [35, 45], 'LR_DECAY': 0.1, 'LR_CLIP': 0.0000001,
+                         'LR_WARMUP': False, 'WARMUP_EPOCH': 1, 'GRAD_NORM_CLIP': 10},
+        'ACTIVE_TRAIN': {'METHOD': 'random', 'PRE_TRAIN_SAMPLE_NUMS': 100, 'SELECT_NUMS': 100, 'TOTAL_BUDGET_NUMS': 600},
+    })
+
+
 def pv_rcnn_llal_cfg():
     """values of tools/cfgs/active-kitti_models/pv_rcnn_active_llal.yaml: the KITTI PV-RCNN with the LLAL loss-prediction module
     (ROI_HEAD.LOSS_NET), no MC-dropout rounds, the loss net frozen during detector training (OPTIMIZATION.LOSS_NET_SKIP) and

@@ -33,6 +33,9 @@ __all__['PointPillar'] = PointPillar
 from .centerpoint import CenterPoint
 __all__['CenterPoint'] = CenterPoint
 
+from .part_a2_net import PartA2Net
+__all__['PartA2Net'] = PartA2Net
+
 
 def build_detector(model_cfg, num_class, dataset):
     return __all__[model_cfg.NAME](model_cfg=model_cfg, num_class=num_class, dataset=dataset)

@@ -79,3 +79,53 @@ class RoIAwarePool3dFunction(Function):
                                                ptr(grad_in), method, cur_stream(g.device)),
               'crb_roiaware_pool3d_backward')
         return None, None, grad_in, None, None, None
+
+
+class DenseRouteNeeded(Exception):
+    """the sparse pooling met an input on which its row rule is not the dense route's (a negative part feature inside a RoI)"""
+
+
+class RoIAwarePoolSparseFunction(Function):
+    """RoI-aware pooling of all frames as the rows of the sparse RoI-grid tensor (crbhip/roiaware_sparse.py): avg of `part`,
+    max of `feat` over the first max_pts - 1 points of every cell, only for the cells the dense route's
+    `pooled_part.sum(-1).nonzero()` would keep."""
+
+    @staticmethod
+    def forward(ctx, rois, pts, frame_offsets, part, feat, out_size, max_pts_each_voxel, extra_flags, extra_out):
+        """rois (B,R,7), pts (N,3), frame_offsets (B+1) i32, part (N,4), feat (N,C)
+        -> coords (T,4) i32 [b*R + r, x, y, z], part (T,4), feat (T,C), argmax (T,C) i32.
+        extra_flags: optional i32 device tensor of the caller's that rides in the op's one read-back; its values are
+        appended to the list extra_out."""
+        from crbhip import roiaware_sparse
+        ret = roiaware_sparse.forward(rois, pts, frame_offsets, part, feat, out_size, max_pts_each_voxel,
+                                      extra_flags=extra_flags)
+        sp, extra = (ret[0], ret[1:]) if extra_flags is not None else (ret, ())
+        if extra_out is not None:
+            extra_out.extend(extra)
+        if sp is None:
+            raise DenseRouteNeeded()
+        ctx.sparse_pool = sp
+        ctx.n_points = pts.shape[0]
+        ctx.mark_non_differentiable(sp.coords, sp.argmax)
+        return sp.coords, sp.part, sp.feat, sp.argmax
+
+    @staticmethod
+    def backward(ctx, g_coords, g_part, g_feat, g_argmax):
+        from crbhip import roiaware_sparse
+        sp = ctx.sparse_pool
+        if g_part is None:
+            g_part = torch.zeros_like(sp.part)
+        if g_feat is None:
+            g_feat = torch.zeros_like(sp.feat)
+        grad_part, grad_feat = roiaware_sparse.backward(sp, ctx.n_points, g_part, g_feat)
+        return None, None, None, grad_part, grad_feat, None, None, None, None
+
+
+def roiaware_pool_sparse(rois, pts, frame_offsets, part, feat, out_size, max_pts_each_voxel=128, extra_flags=None,
+                         extra_out=None):
+    """-> (coords, part, feat, argmax), or None when the call has to take the dense route (DenseRouteNeeded)"""
+    try:
+        return RoIAwarePoolSparseFunction.apply(rois, pts, frame_offsets, part, feat, out_size, max_pts_each_voxel,
+                                                extra_flags, extra_out)
+    except DenseRouteNeeded:
+        return None

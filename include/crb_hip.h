@@ -584,6 +584,41 @@ int crb_roiaware_pool3d_backward(int N, int C, int max_pts_each_voxel, int out_x
                                  const float* grad_out, float* grad_in, int pool_method, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * a15' RoI-aware pooling of all frames straight into the rows of the sparse RoI-grid tensor (csrc/roiaware_sparse.hip)
+ * replaces: the per-frame loop of pcdet/models/roi_heads/partA2_head.py:71-89 (two RoIAwarePool3d calls per frame) and the
+ *           dense -> sparse conversion at :105-117 (`pooled_part.sum(-1).nonzero()` + gather) and their backward.
+ * rois (B*R,7), pts (N,3) stacked frame after frame with frame_offsets (B+1) i32, part (N,4) avg-pooled, feat (N,C)
+ * max-pooled; all f32 device, 16-byte aligned rows of part. Cell membership, the first max_pts-1 points per cell in
+ * ascending point index, avg and max are those of crb_roiaware_pool3d_forward. A cell becomes a ROW iff one of its kept
+ * points has a non-zero part feature: for non-negative part features that is the dense rule "the f32 sum of the four
+ * averages != 0" (DESIGN.md section 7 names the inputs on which the two could differ). *flag bit 0 is raised when a point
+ * inside a RoI carries a negative part feature: the result then follows another rule than the dense route's and must be
+ * discarded.
+ *   count:  roi_counts (B*R,2) i32 = {rows, kept hits} of every RoI; zeroes and sets *flag. out_x*out_y*out_z must be
+ *           <= crb_roiaware_sparse_max_cells() (per-wave LDS histogram), else CRB_ERR_UNSUPPORTED.
+ *   fill:   roi_starts (B*R,2) i32 = the exclusive scan of roi_counts over the RoIs, T / H its two totals ->
+ *           coords (T,4) i32 rows (b*R + r, x, y, z) in lexicographic order, row_ptr (T+1) i32, hit_pt (H) i32 point of
+ *           every kept hit row after row in point order, hit_row (H) i32 its row. Every element is written.
+ *   pool:   out_part (T,4), out_feat (T,C), argmax (T,C) i32 (index into the stacked points). Every element is written.
+ *   backward: grad_part (N,4) / grad_feat (N,C), every element written (exact zero for a point that no row keeps); each is the
+ *           sum over the point's rows in ascending row order - no float atomics, bit-identical between runs. No read-back.
+ * ---------------------------------------------------------------------------------------------- */
+int crb_roiaware_sparse_max_cells(void);
+int crb_roiaware_sparse_count(int n_rois, int R, int B, int64_t N, int max_pts_each_voxel, int out_x, int out_y, int out_z,
+                              const float* rois, const float* pts, const int32_t* frame_offsets, const float* part,
+                              int32_t* roi_counts, int32_t* flag, void* stream);
+int crb_roiaware_sparse_fill(int n_rois, int R, int B, int64_t N, int max_pts_each_voxel, int out_x, int out_y, int out_z,
+                             const float* rois, const float* pts, const int32_t* frame_offsets, const float* part,
+                             const int32_t* roi_starts, int64_t T, int64_t H, int32_t* coords, int32_t* row_ptr,
+                             int32_t* hit_pt, int32_t* hit_row, void* stream);
+int crb_roiaware_sparse_pool(int64_t T, int C, const int32_t* row_ptr, const int32_t* hit_pt, const float* part,
+                             const float* feat, float* out_part, float* out_feat, int32_t* argmax, void* stream);
+int64_t crb_roiaware_sparse_backward_workspace_bytes(int64_t N, int64_t H);
+int crb_roiaware_sparse_backward(int64_t N, int64_t T, int64_t H, int C, const int32_t* row_ptr, const int32_t* hit_pt,
+                                 const int32_t* hit_row, const int32_t* argmax, const float* g_part, const float* g_feat,
+                                 float* grad_part, float* grad_feat, void* workspace, int64_t workspace_bytes, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * a28  CRB stage 3: greedy point-cloud-density balancing
  * replaces: the sklearn KernelDensity / scipy.stats.entropy triple loop of
  *           pcdet/query_strategies/crb_sampling.py:276-331 (SELECT_NUMS x candidates x classes KDE fits on the CPU).

@@ -1,5 +1,5 @@
 #!/usr/bin/env python
-"""Part-A2 point-head timings on one MI355X, one process:
+"""Part-A2 timings on one MI355X, one process:
   targets : crb_part_targets (one launch for all frames) against the reference's route written out here - a loop over the frames, each
             with a boolean-mask gather, two points_in_boxes_gpu queries, the label arithmetic and the part-label expressions
             (pcdet/models/dense_heads/point_head_template.py:74-122);
@@ -11,8 +11,15 @@ tests use). --batch frames of --rows voxel centres each (ragged: frame b has row
 rows; half of the points inside enlarged boxes. Both routes are checked against each other at the timed size before anything is timed.
 Host time around a device synchronise (the reference's route stalls on the host, which device events between launches would not
 show), samples of the two routes alternating; per figure median, p10 and p90 over --steps samples after --warmup. No pass / fail time
-is set. Run it under a time limit. The detector's training step is not timed here: the tree has no Part-A2 detector yet.
+is set. Run it under a time limit.
+  pooling : the RoI-aware pooling of PartA2FCHead forward + backward with its peak memory, sparse route (csrc/roiaware_sparse.hip: one
+            launch sequence for all frames, rows of the sparse tensor) against the dense route (two RoIAwarePool3d calls per frame,
+            `sum(-1).nonzero()`, gather), on what PartA2Net hands its RoI head for --batch synthetic KITTI frames: UNetV2's voxel
+            centres and 16 point features, the point head's part offsets and scores, 128 RoIs per frame sampled from proposals drawn
+            around the ground truths, POOL_SIZE 12, 128 points per cell;
+  step    : PartA2Net (parta2_net_cfg, DP_RATIO as in the yaml) forward + backward on those frames in frames/s, both routes.
 Usage: python tools/time_parta2.py [--batch 16] [--rows 16000] [--boxes 30] [--slots 40] [--steps 30] [--warmup 5]
+                                   [--legs head,pooling,step] [--points 16384]
 Prints one JSON line."""
 import argparse
 import json
@@ -121,6 +128,115 @@ def reference_losses(cls_preds, part_preds, labels, part_labels, loss_fn):
     return loss_cls, loss_part
 
 
+def detector_batch(B, n_points, dev, seed=9):
+    """B synthetic KITTI frames with 128 proposals per frame drawn around the ground truths"""
+    import numpy as np
+    import torch
+    from pcdet.datasets.synthetic import kitti_batch
+    pts, off, gt = kitti_batch(500, B, n_points)
+    rng = np.random.default_rng(seed)
+    rois = np.zeros((B, 128, 7), np.float32)
+    labels = np.ones((B, 128), np.int64)
+    for b in range(B):
+        real = gt[b][gt[b][:, 7] > 0]
+        for r in range(128):
+            g = real[r % len(real)]
+            rois[b, r] = g[:7] + np.concatenate([rng.normal(0, 0.3, 3), g[3:6] * rng.uniform(-0.1, 0.2, 3), rng.normal(0, 0.15, 1)])
+            labels[b, r] = int(g[7])
+    bidx = np.repeat(np.arange(B, dtype=np.float32), np.diff(off))[:, None]
+
+    def batch():
+        return {'points': torch.from_numpy(np.concatenate([bidx, pts], 1)).to(dev), 'point_frame_offsets': torch.from_numpy(off).to(dev),
+                'gt_boxes': torch.from_numpy(gt).to(dev), 'batch_size': B, 'rois': torch.from_numpy(rois).to(dev),
+                'roi_scores': torch.ones((B, 128), device=dev), 'roi_labels': torch.from_numpy(labels).to(dev)}
+    return batch
+
+
+def _peak_of(fn):
+    import torch
+    torch.cuda.synchronize()
+    torch.cuda.reset_peak_memory_stats()
+    base = torch.cuda.memory_allocated()
+    fn()
+    torch.cuda.synchronize()
+    return (torch.cuda.max_memory_allocated() - base) / 1e6
+
+
+def detector_legs(args, dev, legs):
+    import torch
+    from crbhip import roiaware_sparse
+    from crbhip.part_head import frame_offsets
+    from pcdet.datasets import SyntheticDataset
+    from pcdet.model_cfgs import parta2_net_cfg
+    from pcdet.models import build_network
+    from pcdet.ops.roiaware_pool3d.roiaware_pool3d_utils import roiaware_pool_sparse
+    torch.manual_seed(0)
+    cfg = parta2_net_cfg('kitti')
+    model = build_network(cfg.MODEL, 3, SyntheticDataset(num_frames=2, n_points=args.points)).to(dev)
+    model.train()
+    batch = detector_batch(args.batch, args.points, dev)
+    out = {}
+
+    def step():
+        model.zero_grad(set_to_none=True)
+        ret, _, _ = model(batch())
+        ret['loss'].backward()
+        return ret['loss']
+    if 'pooling' in legs:
+        bd = batch()
+        with torch.no_grad():
+            model(bd)
+        head = model.roi_head
+        rois = bd['rois'][..., :7].contiguous()
+        frame = bd['point_coords'][:, 0].contiguous()
+        xyz = bd['point_coords'][:, 1:4].contiguous()
+        off = frame_offsets(frame.view(-1, 1), args.batch)
+        part0, feat0 = head.part_features(bd).detach(), bd['point_features'].detach()
+        pool = head.roiaware_pool3d_layer
+
+        def sparse():
+            part, feat = part0.clone().requires_grad_(True), feat0.clone().requires_grad_(True)
+            c, p, f, _ = roiaware_pool_sparse(rois, xyz, off, part, feat, pool.out_size, pool.max_pts_each_voxel)
+            torch.autograd.backward([p, f], [torch.ones_like(p), torch.ones_like(f)])
+            return c, p, f, part.grad, feat.grad
+
+        def dense():
+            part, feat = part0.clone().requires_grad_(True), feat0.clone().requires_grad_(True)
+            pp, pr = [], []
+            for b in range(args.batch):
+                m = frame == b
+                cur_xyz, cur_roi = xyz[m].contiguous(), rois[b].contiguous()
+                pp.append(pool(cur_roi, cur_xyz, part[m].contiguous(), pool_method='avg'))
+                pr.append(pool(cur_roi, cur_xyz, feat[m].contiguous(), pool_method='max'))
+            pp, pr = torch.cat(pp), torch.cat(pr)
+            idx = pp.sum(dim=-1).nonzero()
+            r, x, y, z = idx.unbind(1)
+            p, f = pp[r, x, y, z], pr[r, x, y, z]
+            torch.autograd.backward([p, f], [torch.ones_like(p), torch.ones_like(f)])
+            return idx.int(), p, f, part.grad, feat.grad
+        a, b = sparse(), dense()
+        agree = {'rows': int(a[0].shape[0]), 'points': int(xyz.shape[0]), 'coords_equal': bool(torch.equal(a[0], b[0])),
+                 'part_equal': bool(torch.equal(a[1], b[1])), 'feat_equal': bool(torch.equal(a[2], b[2])),
+                 'grad_part_max_diff': float((a[3] - b[3]).abs().max()), 'grad_feat_max_diff': float((a[4] - b[4]).abs().max())}
+        assert agree['coords_equal'] and agree['part_equal'] and agree['feat_equal'], agree
+        del a, b
+        t = _timed_pair({'sparse': sparse, 'dense': dense}, args.steps, args.warmup)
+        t['sparse']['peak_mb'], t['dense']['peak_mb'] = _peak_of(sparse), _peak_of(dense)
+        t['speedup_median'] = t['dense']['median_ms'] / t['sparse']['median_ms']
+        t['agreement'] = agree
+        out['pooling_forward_backward'] = t
+    if 'step' in legs:
+        res = {}
+        for name, on in (('sparse', True), ('dense', False)):
+            roiaware_sparse.ENABLED = on
+            st = _timed_pair({name: step}, args.steps, args.warmup)[name]
+            st['frames_per_s'] = args.batch / (st['median_ms'] * 1e-3)
+            res[name] = st
+        roiaware_sparse.ENABLED = True
+        out['training_step'] = res
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--batch', type=int, default=16)
@@ -129,9 +245,15 @@ def main():
     ap.add_argument('--slots', type=int, default=40)
     ap.add_argument('--steps', type=int, default=30)
     ap.add_argument('--warmup', type=int, default=5)
+    ap.add_argument('--legs', default='head,pooling,step')
+    ap.add_argument('--points', type=int, default=16384)
     args = ap.parse_args()
+    legs = args.legs.split(',')
     import torch
     assert torch.cuda.is_available(), 'needs an MI355X'
+    if 'head' not in legs:
+        print(json.dumps(detector_legs(args, torch.device('cuda', 0), legs)))
+        return
     from crbhip import part_head
     from pcdet.utils import loss_utils
     assert part_head.FUSED
@@ -171,6 +293,7 @@ def main():
     out['losses_forward_backward'] = t
     for k in ('targets', 'losses_forward_backward'):
         out[k]['speedup_median'] = out[k]['reference_route']['median_ms'] / out[k]['fused']['median_ms']
+    out.update(detector_legs(args, dev, legs))
     print(json.dumps(out))
 
 
