@@ -85,18 +85,28 @@ __global__ __launch_bounds__(64) void nms_mask_kernel(const float* __restrict__ 
   unsigned long long t = 0;
   const int start = (row_blk == col_blk) ? threadIdx.x + 1 : 0;
   if constexpr (ROTATED) {
-    // Two passes. (1) cheap reject with circumscribed circles: boxes whose BEV centres are farther apart than the sum of
-    // their half-diagonals (+1e-4 relative slack) cannot intersect, the reference's polygon clipping finds no vertex for
-    // them and returns overlap 0 -> IoU 0 -> never above a positive threshold. (2) the rotated-overlap arithmetic only for
-    // the survivors: a wave runs max-over-lanes(survivors) iterations instead of 64 (proposals are score-sorted, i.e.
-    // spatially random: typically a handful of the 64 columns are near a given row box).
+    // Two passes. (1) cheap reject with circumscribed circles, widened by the reference's corner margin; (2) the rotated-overlap
+    // arithmetic only for the survivors: a wave runs max-over-lanes(survivors) iterations instead of 64 (proposals are
+    // score-sorted, i.e. spatially random: typically a handful of the 64 columns are near a given row box).
+    //
+    // A rejected pair must have reference overlap exactly 0, and disjoint boxes do not: the reference counts a corner that lies up
+    // to 1e-2 outside the other box as inside it (in_box_margin), so two boxes end to end with a 9 mm gap get the area of the
+    // strip between them, and two 4 mm boxes 8 mm apart an IoU of 4,800. The overlap is 0 when the polygon has no vertex, and a
+    // vertex is either a crossing of two edges (the boxes intersect: d <= ra + rb for the centre distance d and the half-diagonals
+    // ra, rb) or a corner of one box inside the other grown by m = 1e-2 on every side. The grown box B lies within
+    // |(l/2 + m, w/2 + m)| <= rb + m * sqrt(2) of its centre and a corner of A at ra from A's centre, so a vertex exists only if
+    //   d <= ra + rb + m * sqrt(2) = ra + rb + 0.014143.
+    // kRejectPad = 0.015 leaves 8.6e-4 for the f32 rounding of the reference's corner arithmetic (two roundings at the size of a
+    // coordinate for a corner, the differences and the rotation in in_box_margin: below 8 ulp of a coordinate, 4.9e-4 at 1 km from
+    // the origin, 6e-5 inside a 128 m range); the relative slack 1e-4 on the squared sum covers the rounding of this test itself.
+    constexpr float kRejectPad = 0.015f;
     const float ra = 0.5f * sqrtf(a[3] * a[3] + a[4] * a[4]);
     unsigned long long cand = 0;
     for (int j = start; j < col_size; ++j) {
       const float* b = cb + j * 7;
       const float rb = 0.5f * sqrtf(b[3] * b[3] + b[4] * b[4]);
-      const float dx = a[0] - b[0], dy = a[1] - b[1], rs = ra + rb;
-      if (dx * dx + dy * dy <= rs * rs * 1.0001f + 1e-6f) cand |= 1ULL << j;
+      const float dx = a[0] - b[0], dy = a[1] - b[1], rs = ra + rb + kRejectPad;
+      if (dx * dx + dy * dy <= rs * rs * 1.0001f) cand |= 1ULL << j;
     }
     if (!(thresh > 0.f)) cand = (col_size >= 64 ? ~0ULL : ((1ULL << col_size) - 1ULL)) & (~0ULL << start);  // degenerate threshold: test everything
     while (cand) {

@@ -75,6 +75,9 @@ __global__ __launch_bounds__(256) void kitti_overlaps_kernel(const int64_t* __re
   const float a[7] = {0.f, 0.f, 0.f, (float)gc[3], (float)gc[5], 0.f, -(float)gc[6]};
   const float b[7] = {(float)(dc[0] - gc[0]), (float)(dc[2] - gc[2]), 0.f, (float)dc[3], (float)dc[5], 0.f, -(float)dc[6]};
   const float reach = 0.5f * (sqrtf(a[3] * a[3] + a[4] * a[4]) + sqrtf(b[3] * b[3] + b[4] * b[4]));
+  // The reach does not include kMargin, on purpose: the yardstick here is the reference's f64 clipper, which has no margin and
+  // gives disjoint rectangles exactly 0 - as this reject does. (The NMS reject of csrc/iou3d_nms.hip has to include its margin:
+  // its reference counts corners inside the margin and returns a non-zero overlap for disjoint boxes.)
   float inter = 0.f;
   if (b[0] * b[0] + b[1] * b[1] <= reach * reach) inter = rect_overlap(a, b, kMargin);
   double bev = 0.0, d3 = 0.0;
