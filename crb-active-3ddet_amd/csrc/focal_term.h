@@ -1,4 +1,5 @@
-// The sigmoid focal term of one logit, shared by csrc/point_head.hip and csrc/part_head.hip.
+// The sigmoid focal term of one logit, shared by csrc/point_head.hip, csrc/part_head.hip and, through csrc/rpn_loss_terms.h,
+// csrc/rpn_loss.hip and csrc/multihead_loss.hip.
 #pragma once
 #include <hip/hip_runtime.h>
 

@@ -18,10 +18,11 @@
 // Sums are taken in a fixed order (per-thread, wave shuffle tree, 4 waves, blocks in index order): bit-reproducible.
 #include "crb_common.h"
 #include "../../include/crb_hip.h"
+#include "rpn_loss_terms.h"      // the per-anchor terms and the fixed-order reductions, shared with multihead_loss.hip
 
 namespace {
 
-constexpr int TPB = 256;
+constexpr int TPB = RPN_TPB;
 constexpr int MAX_NC = 8, MAX_NB = 8;
 
 struct RpnArgs {
@@ -36,95 +37,6 @@ struct RpnArgs {
   float cw[7];
   float w_cls, w_loc, w_dir;
 };
-
-// focal term of one logit: loss = aw * pt^gamma * bce, d = d loss / d x      (loss_utils.py:47-72)
-__device__ __forceinline__ void focal_term(float x, bool t, float alpha, float gamma, float& loss, float& d) {
-  const float p = 1.0f / (1.0f + expf(-x));
-  const float bce = fmaxf(x, 0.0f) - (t ? x : 0.0f) + log1pf(expf(-fabsf(x)));
-  const float pt = t ? 1.0f - p : p;
-  const float aw = t ? alpha : 1.0f - alpha;
-  float ptg, ptg1;
-  if (gamma == 2.0f) {
-    ptg = pt * pt;
-    ptg1 = 2.0f * pt;
-  } else {
-    ptg = powf(pt, gamma);
-    ptg1 = gamma * powf(pt, gamma - 1.0f);
-  }
-  loss = aw * ptg * bce;
-  const float dpt = t ? -p * (1.0f - p) : p * (1.0f - p);
-  // d bce / dx = [x >= 0] - t - sign(x) e^-|x| / (1 + e^-|x|) as autograd differentiates the reference's expression
-  // (clamp(x, min=0) - x t + log1p(exp(-|x|))): p - t everywhere except at x == 0 exactly, where sign(0) = 0 leaves 1 - t
-  const float dbce = x == 0.0f ? (t ? 0.0f : 1.0f) : (t ? p - 1.0f : p);
-  d = aw * (ptg1 * dpt * bce + ptg * dbce);
-}
-
-// smooth-L1 of one weighted difference: loss, d loss / d diff      (loss_utils.py:98-107)
-__device__ __forceinline__ void smooth_l1(float diff, float beta, float& loss, float& d) {
-  const float n = fabsf(diff);
-  if (beta < 1e-5f) {
-    loss = n;
-    d = diff > 0.0f ? 1.0f : (diff < 0.0f ? -1.0f : 0.0f);
-  } else if (n < beta) {
-    loss = 0.5f * n * n / beta;
-    d = diff / beta;
-  } else {
-    loss = n - 0.5f * beta;
-    d = diff > 0.0f ? 1.0f : -1.0f;
-  }
-}
-
-// regression term of a positive anchor: sum over the 7 code entries, gradient w.r.t. the 7 predictions
-__device__ __forceinline__ float box_term(const float* __restrict__ p, const float* __restrict__ t, const RpnArgs& a,
-                                          float* __restrict__ g) {
-  float sum = 0.0f;
-#pragma unroll
-  for (int d = 0; d < 7; ++d) {
-    float pv = p[d], tv = t[d], scale = 1.0f;
-    if (d == 6) {                                  // sin(a - b) = sin a cos b - cos a sin b, as the reference encodes it
-      const float sp = sinf(p[6]), cp = cosf(p[6]), st = sinf(t[6]), ct = cosf(t[6]);
-      pv = sp * ct;
-      tv = cp * st;
-      scale = cp * ct + sp * st;                   // d (pv - tv) / d p6
-    }
-    float diff = (tv != tv) ? 0.0f : (pv - tv);    // NaN target -> target := input (loss_utils.py:119)
-    if (tv != tv) scale = 0.0f;
-    diff *= a.cw[d];
-    float l, dl;
-    smooth_l1(diff, a.beta, l, dl);
-    sum += l;
-    if (g) g[d] = dl * a.cw[d] * scale;
-  }
-  return sum;
-}
-
-// direction bin of a positive anchor      (anchor_head_template.py:154-166, common_utils.limit_period)
-__device__ __forceinline__ int dir_bin(float t6, float anchor_rot, const RpnArgs& a) {
-  const float two_pi = 6.283185307179586f;
-  const float rot_gt = t6 + anchor_rot;
-  const float val = rot_gt - a.dir_offset;
-  const float off = val - floorf(val / two_pi + 0.0f) * two_pi;
-  int bin = (int)floorf(off / (two_pi / (float)a.NB));
-  return min(max(bin, 0), a.NB - 1);
-}
-
-// cross entropy of NB logits with target bin: loss, gradient = softmax - onehot
-__device__ __forceinline__ float dir_term(const float* __restrict__ x, int nb, int bin, float* __restrict__ g) {
-  float m = x[0];
-  for (int k = 1; k < nb; ++k) m = fmaxf(m, x[k]);
-  float s = 0.0f;
-  for (int k = 0; k < nb; ++k) s += expf(x[k] - m);
-  const float lse = logf(s);
-  if (g)
-    for (int k = 0; k < nb; ++k) g[k] = expf(x[k] - m - lse) - (k == bin ? 1.0f : 0.0f);
-  return -(x[bin] - m - lse);
-}
-
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-  return v;
-}
 
 constexpr int FWD_PER_THREAD = 4;      // anchors per thread of the forward pass (strided by the block: coalesced label loads)
 
@@ -150,65 +62,12 @@ __global__ __launch_bounds__(TPB) void rpn_loss_partial_kernel(RpnArgs a, float*
     if (lab > 0) {
       s_pos += 1.0f;
       const float* t = a.tgt + (fb + i) * 7;
-      s_loc += box_term(a.box + (fb + i) * 7, t, a, nullptr);
-      if (a.dir) s_dir += dir_term(a.dir + (fb + i) * a.NB, a.NB, dir_bin(t[6], a.anchors[(int64_t)i * 7 + 6], a), nullptr);
+      s_loc += box_term<true>(a.box + (fb + i) * 7, t, a.cw, a.beta, nullptr);
+      if (a.dir)
+        s_dir += dir_term(a.dir + (fb + i) * a.NB, a.NB, dir_bin(t[6], a.anchors[(int64_t)i * 7 + 6], a.dir_offset, a.NB), nullptr);
     }
   }
-  __shared__ float red[TPB / 64][4];
-  s_cls = wave_sum(s_cls);
-  s_loc = wave_sum(s_loc);
-  s_dir = wave_sum(s_dir);
-  s_pos = wave_sum(s_pos);
-  const int w = threadIdx.x >> 6;
-  if ((threadIdx.x & 63) == 0) {
-    red[w][0] = s_cls;
-    red[w][1] = s_loc;
-    red[w][2] = s_dir;
-    red[w][3] = s_pos;
-  }
-  __syncthreads();
-  if (threadIdx.x < 4) {
-    float v = 0.0f;
-#pragma unroll
-    for (int k = 0; k < TPB / 64; ++k) v += red[k][threadIdx.x];
-    partial[((int64_t)b * nblk + blockIdx.x) * 4 + threadIdx.x] = v;
-  }
-}
-
-// one block per frame: partials summed in block order -> loss (B,3) weighted and normalised, npos (B)
-__global__ __launch_bounds__(TPB) void rpn_loss_finalize_kernel(const float* __restrict__ partial, int nblk, float w_cls,
-                                                                float w_loc, float w_dir, float* __restrict__ loss,
-                                                                float* __restrict__ npos) {
-  const int b = blockIdx.x;
-  // thread t sums the partials t, t+256, ... (fixed order), then the fixed tree over the 256 threads
-  float v[4] = {0.0f, 0.0f, 0.0f, 0.0f};
-  for (int k = threadIdx.x; k < nblk; k += TPB) {
-    const float4 p = *reinterpret_cast<const float4*>(partial + ((int64_t)b * nblk + k) * 4);
-    v[0] += p.x;
-    v[1] += p.y;
-    v[2] += p.z;
-    v[3] += p.w;
-  }
-  __shared__ float red[TPB / 64][4];
-#pragma unroll
-  for (int j = 0; j < 4; ++j) v[j] = wave_sum(v[j]);
-  if ((threadIdx.x & 63) == 0)
-#pragma unroll
-    for (int j = 0; j < 4; ++j) red[threadIdx.x >> 6][j] = v[j];
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    float s[4];
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      s[j] = 0.0f;
-      for (int k = 0; k < TPB / 64; ++k) s[j] += red[k][j];
-    }
-    const float norm = fmaxf(s[3], 1.0f);
-    loss[b * 3 + 0] = s[0] / norm * w_cls;
-    loss[b * 3 + 1] = s[1] / norm * w_loc;
-    loss[b * 3 + 2] = s[2] / norm * w_dir;
-    npos[b] = s[3];
-  }
+  block_partial_store(s_cls, s_loc, s_dir, s_pos, partial + ((int64_t)b * nblk + blockIdx.x) * 4);
 }
 
 // gradients of sum_b sum_k gout[b,k] * loss[b,k] w.r.t. the three prediction tensors; a block = 256 consecutive anchors of a
@@ -241,8 +100,8 @@ __global__ __launch_bounds__(TPB) void rpn_loss_backward_kernel(RpnArgs a, const
     for (int k = 0; k < MAX_NB; ++k) gd[k] = 0.0f;
     if (lab > 0) {
       const float* t = a.tgt + (fb + i) * 7;
-      box_term(a.box + (fb + i) * 7, t, a, gb);
-      if (a.dir) dir_term(a.dir + (fb + i) * a.NB, a.NB, dir_bin(t[6], a.anchors[(int64_t)i * 7 + 6], a), gd);
+      box_term<true>(a.box + (fb + i) * 7, t, a.cw, a.beta, gb);
+      if (a.dir) dir_term(a.dir + (fb + i) * a.NB, a.NB, dir_bin(t[6], a.anchors[(int64_t)i * 7 + 6], a.dir_offset, a.NB), gd);
     }
 #pragma unroll
     for (int d = 0; d < 7; ++d) s_box[threadIdx.x * 7 + d] = gb[d] * g_loc;

@@ -81,6 +81,27 @@ def second_iou_cfg():
     return c
 
 
+def second_multihead_cfg():
+    """values of tools/cfgs/kitti_models/second_multihead.yaml: the KITTI SECOND trunk + AnchorHeadMulti (a 64-filter shared 3 x 3
+    convolution, one identity head per class with its own class column, every anchor bottom at -1.6) and per-class NMS"""
+    c = second_cfg('kitti')
+    m = c.MODEL
+    anchors = [_anchor('Car', [3.9, 1.6, 1.56], -1.6, 0.6, 0.45), _anchor('Pedestrian', [0.8, 0.6, 1.73], -1.6, 0.5, 0.35),
+               _anchor('Cyclist', [1.76, 0.6, 1.73], -1.6, 0.5, 0.35)]
+    head = _dense_head(anchors)
+    head.update({'NAME': 'AnchorHeadMulti', 'USE_MULTIHEAD': True, 'SEPARATE_MULTIHEAD': True, 'SHARED_CONV_NUM_FILTER': 64,
+                 'RPN_HEAD_CFGS': [{'HEAD_CLS_NAME': ['Car']}, {'HEAD_CLS_NAME': ['Pedestrian']}, {'HEAD_CLS_NAME': ['Cyclist']}]})
+    m.DENSE_HEAD = EasyDict(head)
+    m.POST_PROCESSING = EasyDict({
+        'RECALL_THRESH_LIST': [0.3, 0.5, 0.7], 'MULTI_CLASSES_NMS': True, 'SCORE_THRESH': 0.1, 'OUTPUT_RAW_SCORE': False,
+        'EVAL_METRIC': 'kitti',
+        'NMS_CONFIG': {'MULTI_CLASSES_NMS': True, 'NMS_TYPE': 'nms_gpu', 'NMS_THRESH': 0.1, 'NMS_PRE_MAXSIZE': 4096,
+                       'NMS_POST_MAXSIZE': 500}})
+    c.DATA_CONFIG = EasyDict({'DATASET': 'KittiDataset'})
+    c.OPTIMIZATION.update({'DECAY_STEP_LIST': [35, 45], 'LR_DECAY': 0.1, 'LR_CLIP': 0.0000001, 'LR_WARMUP': False, 'WARMUP_EPOCH': 1})
+    return c
+
+
 def voxel_rcnn_cfg():
     """values of tools/cfgs/kitti_models/voxel_rcnn_car.yaml: class Car only, the SECOND trunk with the narrow BEV backbone
     ([64, 128] filters, [128, 128] up-sampling) + VoxelRCNNHead (6^3 grid, voxel-neighbourhood pooling of x_conv2 / x_conv3 /

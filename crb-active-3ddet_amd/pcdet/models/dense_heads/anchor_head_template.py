@@ -76,7 +76,12 @@ class AnchorHeadTemplate(nn.Module):
         """the per-class anchor maps side by side (anchor_head_template.py:245); constants of the head: built once per device"""
         hit = self.__dict__.get('_crb_flat_anchors')
         if hit is None or hit[0] is not self.anchors or hit[1].device != self.anchors[0].device:
-            hit = self.__dict__['_crb_flat_anchors'] = (self.anchors, torch.cat(self.anchors, dim=-3))
+            if self.use_multihead:
+                # (A, code) in the multi-head order: every class's anchors as (size, rot, z, y, x), the classes one after another (:241-243)
+                flat = torch.cat([a.permute(3, 4, 0, 1, 2, 5).contiguous().view(-1, a.shape[-1]) for a in self.anchors], dim=0)
+            else:
+                flat = torch.cat(self.anchors, dim=-3)
+            hit = self.__dict__['_crb_flat_anchors'] = (self.anchors, flat)
         return hit[1]
 
     def get_cls_layer_loss(self, new_data=None, reduce=True):
@@ -222,14 +227,21 @@ class AnchorHeadTemplate(nn.Module):
         tb['rpn_loss'] = (rpn_loss if reduce else rpn_loss[0]).detach()
         return rpn_loss, tb
 
-    def generate_predicted_boxes(self, batch_size, cls_preds, box_preds, dir_cls_preds=None, anchor_idx=None):
+    def generate_predicted_boxes(self, batch_size, cls_preds, box_preds, dir_cls_preds=None, anchor_idx=None, anchors=None):
         """cls (B,H,W,C1), box (B,H,W,C2), dir (B,H,W,C3) -> (B,A,num_class), (B,A,7+C)  (anchor_head_template.py:238-285).
+        Multi-head: lists of per-head (B,A_h,.) tensors in the multi-head anchor order -> the list of class predictions as it is
+        and the boxes of all heads side by side (:246-251).
         anchor_idx (B,k) long: decode ONLY those anchors -> (B,A,num_class), (B,k,7+C) — the rows the full decode would hold at
         these indices (the decode is elementwise per anchor). A two-stage detector reads the RPN boxes through the proposal
-        layer's top-k alone: 9,000 (training) / 1,024 (test) of the 211,200 anchors per frame."""
-        anchors = self._flat_anchors()
+        layer's top-k alone: 9,000 (training) / 1,024 (test) of the 211,200 anchors per frame.
+        anchors (A',7): decode against this anchor list instead of the head's whole one (one head's slice of the multi-head order)."""
+        anchors = self._flat_anchors() if anchors is None else anchors
         A = anchors.view(-1, anchors.shape[-1]).shape[0]
-        batch_cls_preds = cls_preds.view(batch_size, A, -1).float()
+        if isinstance(box_preds, list):
+            box_preds = torch.cat(box_preds, dim=1)
+        if isinstance(dir_cls_preds, list):
+            dir_cls_preds = torch.cat(dir_cls_preds, dim=1)
+        batch_cls_preds = cls_preds if isinstance(cls_preds, list) else cls_preds.view(batch_size, A, -1).float()
         raw = box_preds.view(batch_size, A, -1)
         dirs = dir_cls_preds.view(batch_size, A, -1) if dir_cls_preds is not None else None
         if anchor_idx is not None and FUSED_DECODE and raw.is_cuda and raw.shape[-1] == 7 and anchors.shape[-1] == 7 and \

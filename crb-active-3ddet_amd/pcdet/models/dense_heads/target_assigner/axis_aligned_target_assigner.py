@@ -39,12 +39,14 @@ class AxisAlignedTargetAssigner(object):
         self.unmatched_thresholds = {c['class_name']: c['unmatched_threshold'] for c in anchor_generator_cfg}
         self.use_multihead = model_cfg.get('USE_MULTIHEAD', False)
         self.max_class_id = max(int(np.nonzero(self.class_names == n)[0][0]) + 1 for n in self.anchor_class_names)
-        if self.pos_fraction is not None or self.use_multihead or self.match_height:
-            raise NotImplementedError('only POS_FRACTION<0, single head, nearest-BEV matching are on the hot path')
+        if self.pos_fraction is not None or self.match_height:
+            raise NotImplementedError('only POS_FRACTION<0, nearest-BEV matching are on the hot path')
 
     def assign_targets(self, all_anchors, gt_boxes_with_classes):
         """all_anchors: [(nz,ny,nx,S,R,7) per class]; gt (B,G,8) zero padded, last column class id 1..C
-        -> box_cls_labels (B,A) int32, box_reg_targets (B,A,code), reg_weights (B,A); A ordered (z,y,x,class,size,rot)"""
+        -> box_cls_labels (B,A) int32, box_reg_targets (B,A,code), reg_weights (B,A); A ordered (z,y,x,class,size,rot), with
+        USE_MULTIHEAD (class, size, rot, z, y, x): every class's anchors permuted (3,4,0,1,2,5) and the classes one after another
+        (axis_aligned_target_assigner.py:68-101)"""
         gt = gt_boxes_with_classes
         B, G = gt.shape[0], gt.shape[1]
         if G == 0:
@@ -66,42 +68,59 @@ class AxisAlignedTargetAssigner(object):
         fm_shape = all_anchors[0].shape[:3]
         for c_idx, (cname, anchors) in enumerate(zip(self.anchor_class_names, all_anchors)):
             cid = int(np.nonzero(self.class_names == cname)[0][0]) + 1
-            a = anchors.reshape(-1, anchors.shape[-1])
+            a = self._multihead_order(anchors) if self.use_multihead else anchors.reshape(-1, anchors.shape[-1])
             m = valid & (gt_cls.int() == cid)
             lab, tgt, w = self.assign_targets_batched(a, gt_boxes, m, cid, self.matched_thresholds[cname],
                                                       self.unmatched_thresholds[cname])
+            if self.use_multihead:
+                labels_l.append(lab)
+                targets_l.append(tgt)
+                weights_l.append(w)
+                continue
             labels_l.append(lab.view(B, *fm_shape, -1))
             targets_l.append(tgt.view(B, *fm_shape, -1, self.box_coder.code_size))
             weights_l.append(w.view(B, *fm_shape, -1))
+        if self.use_multihead:
+            return {'box_cls_labels': torch.cat(labels_l, dim=1), 'box_reg_targets': torch.cat(targets_l, dim=1),
+                    'reg_weights': torch.cat(weights_l, dim=1)}
         return {
             'box_cls_labels': torch.cat(labels_l, dim=-1).view(B, -1),
             'box_reg_targets': torch.cat(targets_l, dim=-2).view(B, -1, self.box_coder.code_size),
             'reg_weights': torch.cat(weights_l, dim=-1).view(B, -1),
         }
 
+    @staticmethod
+    def _multihead_order(anchors):
+        """(nz,ny,nx,S,R,code) -> (S*R*nz*ny*nx, code): the anchor order of a SingleHead's (a, H, W) outputs"""
+        return anchors.permute(3, 4, 0, 1, 2, 5).contiguous().view(-1, anchors.shape[-1])
+
     def _fused_constants(self, all_anchors):
         key = (all_anchors[0].device, all_anchors[0].data_ptr())
-        if getattr(self, '_fused_key', None) != key:
-            dev = all_anchors[0].device
+        if getattr(self, '_fused_key', None) == key:
+            return self._fused
+        dev = all_anchors[0].device
+        ids = [int(np.nonzero(self.class_names == n)[0][0]) + 1 for n in self.anchor_class_names]
+        if self.use_multihead:
+            # the kernel takes any anchor list with a class id per anchor (it works anchor by anchor): the multi-head order, where
+            # the classes' maps may differ in size (per-class feature_map_stride)
+            flat = torch.cat([self._multihead_order(a) for a in all_anchors], dim=0)
+            anchor_cls = torch.cat([torch.full((a.numel() // a.shape[-1],), i, dtype=torch.int32) for i, a in zip(ids, all_anchors)])
+        else:
             flat = torch.cat(all_anchors, dim=-3)                       # (nz,ny,nx, sum S, R, 7)
-            per = [a.shape[3] * a.shape[4] for a in all_anchors]
-            ids = [int(np.nonzero(self.class_names == n)[0][0]) + 1 for n in self.anchor_class_names]
-            pattern = torch.tensor(sum([[i] * (a.shape[4]) * a.shape[3] for i, a in zip(ids, all_anchors)], []),
-                                   dtype=torch.int32)
             # flattened order is (.., class*size, rot): class id of slot s = ids[s // R] for equal R per class
             R = all_anchors[0].shape[4]
             slots = torch.tensor(sum([[i] * a.shape[3] for i, a in zip(ids, all_anchors)], []), dtype=torch.int32)
             cls_of = slots.repeat_interleave(R)                          # (sum S * R)
             A = flat.numel() // 7
-            anchor_cls = cls_of.repeat(A // cls_of.numel()).to(dev)
-            nmax = max(ids) + 1
-            m = torch.zeros(nmax, dtype=torch.float32)
-            u = torch.zeros(nmax, dtype=torch.float32)
-            for i, n in zip(ids, self.anchor_class_names):
-                m[i] = self.matched_thresholds[n]
-                u[i] = self.unmatched_thresholds[n]
-            self._fused = (flat.reshape(-1, 7).contiguous(), anchor_cls.contiguous(), m.to(dev), u.to(dev))
-            self._fused_key = key
+            anchor_cls = cls_of.repeat(A // cls_of.numel())
+        nmax = max(ids) + 1
+        m = torch.zeros(nmax, dtype=torch.float32)
+        u = torch.zeros(nmax, dtype=torch.float32)
+        for i, n in zip(ids, self.anchor_class_names):
+            m[i] = self.matched_thresholds[n]
+            u[i] = self.unmatched_thresholds[n]
+        self._fused = (flat.reshape(-1, 7).contiguous(), anchor_cls.to(dev).contiguous(), m.to(dev), u.to(dev))
+        self._fused_key = key
         return self._fused
 
     def assign_targets_fused(self, all_anchors, gt):

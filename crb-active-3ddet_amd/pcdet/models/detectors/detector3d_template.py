@@ -283,7 +283,10 @@ class Detector3DTemplate(nn.Module):
         return m, model_info_dict
 
     def post_processing(self, batch_dict):
-        from .post_processing import crb_post_processing
+        from .post_processing import crb_post_processing, multiclass_post_processing
+        if self.model_cfg.POST_PROCESSING.NMS_CONFIG.get('MULTI_CLASSES_NMS', False) and \
+                isinstance(batch_dict.get('batch_cls_preds', None), list):
+            return multiclass_post_processing(self, batch_dict)         # a multi-head dense head: per-class NMS
         return crb_post_processing(self, batch_dict)
 
     @staticmethod

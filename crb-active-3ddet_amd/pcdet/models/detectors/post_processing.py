@@ -275,6 +275,77 @@ def crb_post_processing(model, batch_dict):
     return pred_dicts, recall_dict
 
 
+def multiclass_post_processing(model, batch_dict):
+    """MULTI_CLASSES_NMS on a multi-head dense head (batch_cls_preds a list of per-head logits): per (frame, head, class) score
+    threshold, NMS_PRE_MAXSIZE best, NMS, NMS_POST_MAXSIZE; a frame's boxes are its segments' survivors in head order, class order
+    inside a head, best first inside a class, labels through multihead_label_mapping — AnchorHeadMulti +
+    model_nms_utils.multi_classes_nms as the reference's post_processing loops them (detector3d_template.py:292-317).
+    The reference's CRB-patched post_processing cannot finish this branch (its record reads `selected` and `final_logits`, which
+    the branch never defines), so there is no record to match: the pred dicts carry pred_boxes, pred_scores, pred_labels as the
+    reference's unpatched detector would, and pred_logits (n, max C_h): the logits of the box's own head at its anchor (zero past the
+    head's columns) — the precedent of CenterPoint.post_processing.
+    Device route: one launch sequence for all segments (model_nms_utils.multi_classes_nms_batched) and ONE read-back of the frame
+    counts. CRB_MULTICLASS_NMS=0 (or a configuration the kernels do not take): the per-segment loop over multi_classes_nms."""
+    from crbhip import multihead
+    from ..dense_heads import anchor_head_multi as ahm
+    from ..model_utils import model_nms_utils
+    cfg = model.model_cfg.POST_PROCESSING
+    nms = cfg.NMS_CONFIG
+    B = batch_dict['batch_size']
+    cls_list = batch_dict['batch_cls_preds']
+    assert not batch_dict['cls_preds_normalized']
+    mapping = batch_dict['multihead_label_mapping']
+    for c, m in zip(cls_list, mapping):
+        assert c.shape[-1] == len(m)
+    cmax = max(int(c.shape[-1]) for c in cls_list)
+    device_route = ahm.MULTICLASS_NMS and cls_list[0].is_cuda and 'multihead_box_decoder' in batch_dict
+    if device_route and (int(nms.NMS_PRE_MAXSIZE) > multihead.MAX_PRE or len(cls_list) > multihead.MAX_HEADS or
+                         cmax > multihead.MAX_HEAD_CLASSES):
+        import warnings
+        warnings.warn('multiclass_post_processing: torch route (NMS_PRE_MAXSIZE %d, %d heads, %d classes in a head beyond the kernels\' '
+                      '%d / %d / %d)' % (nms.NMS_PRE_MAXSIZE, len(cls_list), cmax, multihead.MAX_PRE, multihead.MAX_HEADS,
+                                         multihead.MAX_HEAD_CLASSES))
+        device_route = False
+    frames = []
+    if device_route:
+        rec = model_nms_utils.multi_classes_nms_batched([c.float() for c in cls_list], batch_dict['multihead_box_decoder'], mapping, nms,
+                                                        cfg.SCORE_THRESH)
+        logits = rec['pred_boxes'].new_zeros((B, rec['seg_of'].shape[1], cmax))
+        seg, first = rec['seg_of'].long(), 0
+        for c in cls_list:                                    # the kept boxes' own head's logit rows
+            C = int(c.shape[-1])
+            mine = (seg >= first) & (seg < first + C)
+            rows = torch.gather(c.float(), 1, torch.where(mine, rec['pred_anchor'], torch.zeros_like(seg))[..., None].expand(-1, -1, C))
+            logits[..., :C] += rows * mine[..., None]
+            first += C
+        num = rec['num'].cpu().tolist()                          # the single read-back of the selection
+        for b in range(B):
+            k = num[b]
+            frames.append({'pred_boxes': rec['pred_boxes'][b, :k], 'pred_scores': rec['pred_scores'][b, :k],
+                           'pred_labels': rec['pred_labels'][b, :k], 'pred_logits': logits[b, :k]})
+    else:
+        boxes = batch_dict.get('batch_box_preds', None)
+        if boxes is None:
+            boxes = batch_dict['batch_box_decoder_full']()
+        for b in range(B):
+            out, start = {'pred_boxes': [], 'pred_scores': [], 'pred_labels': [], 'pred_logits': []}, 0
+            for c, m in zip(cls_list, mapping):
+                n, C = int(c.shape[1]), int(c.shape[2])
+                s, l, bx, sel = model_nms_utils.multi_classes_nms(torch.sigmoid(c[b].float()), boxes[b, start:start + n], nms,
+                                                                  cfg.SCORE_THRESH, return_index=True)
+                out['pred_scores'].append(s)
+                out['pred_labels'].append(m.to(l.device)[l])
+                out['pred_boxes'].append(bx)
+                out['pred_logits'].append(torch.nn.functional.pad(c[b].float()[sel], (0, cmax - C)))
+                start += n
+            frames.append({k: torch.cat(v, dim=0) for k, v in out.items()})
+    recall_dict = {}
+    for b in range(B):
+        recall_dict = generate_recall_record(box_preds=frames[b]['pred_boxes'], recall_dict=recall_dict, batch_index=b,
+                                             data_dict=batch_dict, thresh_list=cfg.RECALL_THRESH_LIST)
+    return frames, recall_dict
+
+
 def generate_recall_record(box_preds, recall_dict, batch_index, data_dict=None, thresh_list=None):
     """recall bookkeeping of detector3d_template.py:411-453"""
     if 'gt_boxes' not in data_dict:

@@ -758,6 +758,65 @@ int crb_rpn_loss_backward(const float* cls_preds, const float* box_preds, const 
                           const float* npos, const float* grad_loss, float* d_cls, float* d_box, float* d_dir, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * a11m  RPN losses of AnchorHeadMulti over head slices (csrc/multihead_loss.hip)
+ * replaces: AnchorHeadMulti.get_cls_layer_loss / get_box_reg_layer_loss (pcdet/models/dense_heads/anchor_head_multi.py:245-373)
+ * heads: HOST array of num_heads <= CRB_MULTIHEAD_MAX_HEADS entries. Head h predicts the anchors [anchor_start, anchor_start +
+ * anchor_count) of the multi-head anchor order (classes one after another, each (size, rot, z, y, x)) in its own tensors cls
+ * (B,A_h,C_h), box (B,A_h,7), dir (B,A_h,num_dir_bins) or NULL (all heads or none). Its class columns are the classes class_start + 1 ..
+ * class_start + class_count: column j's target is [label == class_start + j + 1], so a positive whose class lies outside the head's
+ * columns has an all-zero target row (SEPARATE_MULTIHEAD; without it class_start = 0 and class_count = num_class for every head).
+ * cfg->num_class is the head's total class count (== 1: any label > 0 is class 1). labels (B,A) i32, reg_targets (B,A,7), anchors (A,7)
+ * over all heads, A = sum of anchor_count. Classification terms are weighted pos_cls_weight (label > 0), neg_cls_weight (label == 0),
+ * 0 (ignored). The heading column goes through the sine difference only when the heads have a direction classifier, as in the reference.
+ * forward : loss (B,3) = per frame {cls, loc, dir}, each = weight * sum over the anchors of ALL heads / max(npos,1); npos (B) f32.
+ * backward: d_cls / d_box / d_dir of every entry are written whole (zeros where there is no term), in the head's own layout.
+ * Sums are taken in a fixed order: bit-reproducible. Limits: class_count <= 8, num_dir_bins <= 8 (else CRB_ERR_ARG).
+ * ---------------------------------------------------------------------------------------------- */
+#define CRB_MULTIHEAD_MAX_HEADS 16
+typedef struct CrbMultiHeadEntry {
+  const float* cls;              /* (B, anchor_count, class_count) logits */
+  const float* box;              /* (B, anchor_count, 7) */
+  const float* dir;              /* (B, anchor_count, num_dir_bins) or NULL */
+  float* d_cls;                  /* gradients, same shapes (backward only) */
+  float* d_box;
+  float* d_dir;
+  int32_t anchor_start, anchor_count, class_start, class_count;
+} CrbMultiHeadEntry;
+int64_t crb_multihead_loss_workspace_bytes(int B, int A);
+int crb_multihead_loss_forward(const CrbMultiHeadEntry* heads, int num_heads, const int32_t* labels, const float* reg_targets,
+                               const float* anchors, int B, int A, const CrbRpnLossCfg* cfg, float pos_cls_weight,
+                               float neg_cls_weight, float* loss, float* npos, void* workspace, int64_t workspace_bytes,
+                               void* stream);
+int crb_multihead_loss_backward(const CrbMultiHeadEntry* heads, int num_heads, const int32_t* labels, const float* reg_targets,
+                                const float* anchors, int B, int A, const CrbRpnLossCfg* cfg, float pos_cls_weight,
+                                float neg_cls_weight, const float* npos, const float* grad_loss, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * a22  per-class selection of a whole batch: MULTI_CLASSES_NMS on a multi-head detector (csrc/multiclass_nms.hip)
+ * replaces: the frames x heads x classes loop of Detector3DTemplate.post_processing (pcdet/models/detectors/detector3d_template.py:
+ *           292-317) around model_nms_utils.multi_classes_nms (pcdet/models/model_utils/model_nms_utils.py:28-66)
+ * A segment is one (frame, head, class) triple; with SEG = sum of class_count there are S = B * SEG of them, stored HEAD-major: segment
+ * (b, h, c) has the row B * seg_start_h + b * C_h + c (seg_start_h = classes of the heads before h), so that head h's rows are one
+ * contiguous (B, C_h * pre_max) block, the anchor_idx layout of crb_decode_selected_anchors.
+ * crb_multiclass_candidates: heads as above (cls, anchor_count, class_count are read). For every segment the anchors with
+ *   1 / (1 + exp(-logit)) >= score_thresh, of those the best min(pre_max, A_h) in descending order of that f32 score, equal scores by
+ *   ascending anchor index -> top_idx (S,pre_max) i64 into the head's anchors, top_logit (S,pre_max), counts (S) i32; entries past
+ *   counts[s] are 0. One workgroup per segment: count, radix select of the cut when more than the quota pass, compaction and a bitonic
+ *   sort in LDS. Nothing of size (S, A_h) is written. pre_max <= 4096 (else CRB_ERR_UNSUPPORTED).
+ * crb_multiclass_finish: keep (S,post) i32 / num_keep (S) of crb_nms_batched over those segments, top_boxes (S,pre_max,7) the decoded
+ *   picks, label_map (SEG) i64 the class id of every (head, class) column -> per frame the survivors of its segments one after
+ *   another (head order, class order inside a head, best first inside a class): pred_boxes (B,P,7), pred_logit (B,P), pred_labels (B,P)
+ *   i64, pred_anchor (B,P) i64 (index into the head's anchors), seg_of (B,P) i32 (0 .. SEG-1), num (B) i32, P = SEG * post. Rows past num[b]
+ *   are zero.
+ * ---------------------------------------------------------------------------------------------- */
+int crb_multiclass_candidates(const CrbMultiHeadEntry* heads, int num_heads, int B, float score_thresh, int pre_max, int64_t* top_idx,
+                              float* top_logit, int32_t* counts, void* stream);
+int crb_multiclass_finish(const CrbMultiHeadEntry* heads, int num_heads, int B, int pre_max, int post, const int32_t* keep,
+                          const int32_t* num_keep, const int64_t* top_idx, const float* top_logit, const float* top_boxes,
+                          const int64_t* label_map, float* pred_boxes, float* pred_logit, int64_t* pred_labels, int64_t* pred_anchor,
+                          int32_t* seg_of, int32_t* num, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * a21  proposal layer around its NMS (csrc/proposal_layer.hip)
  * crb_decode_selected_anchors replaces AnchorHeadTemplate.generate_predicted_boxes for the anchors the proposal layer keeps
  *   (pcdet/models/dense_heads/anchor_head_template.py:238-285 with ResidualCoder.decode_torch, pcdet/utils/box_coder_utils.py:45-73,
