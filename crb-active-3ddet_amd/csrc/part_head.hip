@@ -16,18 +16,10 @@
 // f32 sums over 1,024 rows or an f32 result cannot stay within four times of.
 #include "crb_common.h"
 #include "focal_term.h"
-#include "pt_in_box.h"
+#include "part_head_common.h"
 #include "../../include/crb_hip.h"
 
 namespace {
-
-constexpr int PT_CHUNK = 64;     // ground truths staged per pass
-constexpr int LOSS_TPB = 256;
-constexpr int LOSS_ROWS = 4;     // rows per thread
-constexpr int LOSS_TILE = LOSS_TPB * LOSS_ROWS;
-
-// a ground truth and its enlarged twin (box_utils.enlarge_box3d: dims + extra width, centre and heading unchanged -> the same sin / cos)
-struct PartBoxLds { BoxLds box; float ex, ey, ez; };
 
 // grid (cdiv(N, 256), B): workgroup (x, b) takes rows off[b] + 256 x .. of frame b and leaves at once when the frame has fewer
 __global__ __launch_bounds__(256) void part_targets_kernel(int G, int num_class, float ew0, float ew1, float ew2,
@@ -47,66 +39,16 @@ __global__ __launch_bounds__(256) void part_targets_kernel(int G, int num_class,
     x = p[1]; y = p[2]; z = p[3];
   }
   const float* fb = gt + (int64_t)b * G * 8;
-  int found = -1;
-  bool shell = false;                                       // some enlarged box contains the point
-  for (int t0 = 0; t0 < G; t0 += PT_CHUNK) {
-    __syncthreads();
-    const int tc = min(PT_CHUNK, G - t0);
-    if ((int)threadIdx.x < tc) {
-      const float* r = fb + (int64_t)(t0 + threadIdx.x) * 8;
-      PartBoxLds v;
-      v.box = load_box(r);
-      v.ex = r[3] + ew0; v.ey = r[4] + ew1; v.ez = r[5] + ew2;
-      sb[threadIdx.x] = v;
-    }
-    __syncthreads();
-    if (active && found < 0) {
-      float lx, ly;
-      for (int k = 0; k < tc; ++k) {
-        if (pt_in_box(x, y, z, sb[k].box, lx, ly)) { found = t0 + k; break; }
-        if (!shell) {
-          BoxLds e = sb[k].box;
-          e.dx = sb[k].ex; e.dy = sb[k].ey; e.dz = sb[k].ez;
-          shell = pt_in_box(x, y, z, e, lx, ly);
-        }
-      }
-    }
-  }
+  bool shell;                                               // some enlarged box contains the point
+  const int found = part_find_owner(sb, fb, G, ew0, ew1, ew2, active, x, y, z, shell);
   if (!active) return;
-  // fg ^ (enlarged hit), then the foreground class on top: an owned point keeps its class whatever the enlarged query says
-  int64_t lab = shell ? -1 : 0;
+  const int64_t lab = part_label(fb, found, shell, num_class);
   float pl[3] = {0.f, 0.f, 0.f};
-  if (found >= 0) {
-    const float* r = fb + (int64_t)found * 8;
-    lab = num_class == 1 ? 1 : (int64_t)r[7];
-    // rotate_z(p - c, -rz) / dims + 0.5 in f64 from the f32 inputs, rounded once
-    const double sx = (double)x - (double)r[0], sy = (double)y - (double)r[1], sz = (double)z - (double)r[2];
-    const double ca = cos((double)r[6]), sa = sin((double)r[6]);
-    pl[0] = (float)((sx * ca + sy * sa) / (double)r[3] + 0.5);
-    pl[1] = (float)((sy * ca - sx * sa) / (double)r[4] + 0.5);
-    pl[2] = (float)(sz / (double)r[5] + 0.5);
-  }
+  if (found >= 0) part_offsets(fb + (int64_t)found * 8, x, y, z, pl);
   labels[i] = lab;
   owner[i] = found;
   part[(int64_t)i * 3] = pl[0]; part[(int64_t)i * 3 + 1] = pl[1]; part[(int64_t)i * 3 + 2] = pl[2];
 }
-
-// sum over the workgroup in a fixed order: xor butterflies inside each wave, then the four wave sums left to right
-template <typename T>
-__device__ __forceinline__ T loss_block_sum(T v, T* sh) {
-#pragma unroll
-  for (int d = 32; d >= 1; d >>= 1) v += __shfl_xor(v, d, 64);
-  __syncthreads();
-  if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = v;
-  __syncthreads();
-  T t = 0;
-#pragma unroll
-  for (int w = 0; w < LOSS_TPB / 64; ++w) t += sh[w];
-  return t;
-}
-
-// stable binary cross entropy of sigmoid(x) against t
-__device__ __forceinline__ float part_bce(float x, float t) { return fmaxf(x, 0.0f) - x * t + log1pf(expf(-fabsf(x))); }
 
 // partials (tiles, 3) f64 = {sum of focal terms over rows with label >= 0, sum of part terms over rows with label > 0, positives}
 __global__ __launch_bounds__(LOSS_TPB) void part_loss_partial_kernel(const float* __restrict__ cls, const float* __restrict__ prt,

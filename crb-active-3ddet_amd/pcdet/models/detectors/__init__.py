@@ -36,6 +36,9 @@ __all__['CenterPoint'] = CenterPoint
 from .part_a2_net import PartA2Net
 __all__['PartA2Net'] = PartA2Net
 
+from .point_rcnn import PointRCNN
+__all__['PointRCNN'] = PointRCNN
+
 
 def build_detector(model_cfg, num_class, dataset):
     return __all__[model_cfg.NAME](model_cfg=model_cfg, num_class=num_class, dataset=dataset)

@@ -84,7 +84,7 @@ def crb_frame_records(model, batch_dict):
     else:
         label_preds = label_preds + 1
     sel, valid, num = final_nms_batched(cls_confs, box_preds, cfg.NMS_CONFIG, cfg.SCORE_THRESH)
-    num_class = len(model.model_cfg.DENSE_HEAD.ANCHOR_GENERATOR_CONFIG)
+    num_class = len(class_names_of(model))
     full = batch_dict.get('full_cls_scores', None)
     if FUSED_RECORDS and box_preds.is_cuda and not cfg.OUTPUT_RAW_SCORE and num_class <= 16 and sel.shape[1] <= 2048 and \
             label_preds.dtype == torch.int64:
@@ -137,7 +137,7 @@ def crb_frame_records(model, batch_dict):
     cnt = _first_hit_counts(idx, P)
     vol = pred_boxes[..., 3] * pred_boxes[..., 4] * pred_boxes[..., 5]
     density = torch.where(valid, cnt[:, :P] / vol.clamp(min=1e-12), torch.zeros_like(vol))
-    num_class = len(model.model_cfg.DENSE_HEAD.ANCHOR_GENERATOR_CONFIG)
+    num_class = len(class_names_of(model))
     ent = label_entropy(pred_labels, valid, num_class)
     rcnn_cls = rcnn_reg = None
     if 'rcnn_cls' in batch_dict and batch_dict['rcnn_cls'].dim() > 2:
@@ -164,8 +164,9 @@ GT_STAT_FIELDS = 5          # num_bbox, n_counted, mean, median, variance per cl
 
 
 def class_names_of(model):
-    anchors = getattr(model.model_cfg.DENSE_HEAD, 'ANCHOR_GENERATOR_CONFIG', None)
-    if anchors is None:                                    # anchor-free dense head (CenterHead): the detector's own class list
+    dense = getattr(model.model_cfg, 'DENSE_HEAD', None)
+    anchors = None if dense is None else getattr(dense, 'ANCHOR_GENERATOR_CONFIG', None)
+    if anchors is None:                # anchor-free dense head (CenterHead) or none at all (PointRCNN): the detector's own class list
         return list(model.class_names)
     return [c['class_name'] for c in anchors]
 

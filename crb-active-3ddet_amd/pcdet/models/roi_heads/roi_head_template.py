@@ -48,24 +48,46 @@ class RoIHeadTemplate(nn.Module):
     def proposal_layer(self, batch_dict, nms_config):
         """batch_cls_preds (B,A,C), batch_box_preds (B,A,7) -> rois (B,POST,7) zero padded, roi_scores, roi_labels (1-based,
         padding = 1 as in the reference), full_cls_scores (B,POST,C)   (roi_head_template.py:45-108).
-        All frames go through one top-k, one batched mask launch and one on-device greedy scan."""
+        All frames go through one top-k, one batched mask launch and one on-device greedy scan. Per-point boxes come dense and
+        frame-padded with batch_counts (B), or stacked (N,C), (N,7) with batch_index (N) and are packed first; a frame with fewer
+        rows than NMS_PRE_MAXSIZE, or none, gives zero-padded rois with label 1."""
         if batch_dict.get('rois', None) is not None:
             return batch_dict
         if nms_config.MULTI_CLASSES_NMS:
             raise NotImplementedError
         box_preds, cls_preds = batch_dict.get('batch_box_preds', None), batch_dict['batch_cls_preds']
-        assert cls_preds.dim() == 3 and batch_dict.get('batch_index', None) is None
+        # per-point boxes (PointIntraPartOffsetHead's box branch, PointHeadBox): frames of different sizes. Dense, frame-padded
+        # (B,Amax,.) tensors with batch_counts (B) from the device route, or the reference's stacked rows with batch_index, packed here
+        counts = batch_dict.pop('batch_counts', None)
+        if batch_dict.get('batch_index', None) is not None:
+            from crbhip.point_box import pack_stacked
+            assert cls_preds.dim() == 2 and box_preds is not None and counts is None
+            cls_preds, box_preds, counts = pack_stacked(batch_dict['batch_index'], cls_preds, box_preds, batch_dict['batch_size'])
+        assert cls_preds.dim() == 3
         B, A = cls_preds.shape[0], cls_preds.shape[1]
         post = nms_config.NMS_POST_MAXSIZE
+        if counts is not None and A == 0:                                           # no row in any frame
+            C = cls_preds.shape[-1]
+            batch_dict.update(rois=box_preds.new_zeros((B, post, box_preds.shape[-1])), roi_scores=box_preds.new_zeros((B, post)),
+                              roi_labels=torch.ones((B, post), dtype=torch.int64, device=box_preds.device),
+                              full_cls_scores=cls_preds.new_zeros((B, post, C)), has_class_labels=True if C > 1 else False)
+            batch_dict.pop('batch_index', None)
+            return batch_dict
         scores, labels = torch.max(cls_preds, dim=2)
         k = min(nms_config.NMS_PRE_MAXSIZE, A)
-        top_scores, top_idx = torch.topk(scores, k=k, dim=1)                       # sorted descending
+        top_scores, top_idx = torch.topk(scores, k=k, dim=1)                       # sorted descending (padding rows, -inf, last)
+        nms_counts = None if counts is None else torch.clamp(counts, max=k)        # min(k, n_b) candidates of frame b
         if box_preds is None:           # the dense head left the decode to us: only the k anchors kept here become boxes
             top_boxes = batch_dict['batch_box_decoder'](top_idx)
         else:
             top_boxes = torch.gather(box_preds, 1, top_idx[..., None].expand(-1, -1, box_preds.shape[-1]))
-        keep, _ = iou3d_nms_utils.nms_batched(top_boxes[..., 0:7].contiguous(), None, nms_config.NMS_THRESH, post,
+        keep, _ = iou3d_nms_utils.nms_batched(top_boxes[..., 0:7].contiguous(), nms_counts, nms_config.NMS_THRESH, post,
                                               rotated=(nms_config.NMS_TYPE == 'nms_gpu'))
+        if counts is not None:
+            # a slot without a kept box reads candidate 0 under a zero mask: in a frame without rows that is a padding row, whose -inf
+            # must not meet the 0
+            pad = torch.isneginf(scores)
+            scores, cls_preds = scores.masked_fill(pad, 0.0), cls_preds.masked_fill(pad[..., None], 0.0)
         if FUSED_PROPOSAL and cls_preds.is_cuda and top_idx.dtype == torch.int64:
             from crbhip import lib, check, ptr, cur_stream
             C, bc, dev = int(cls_preds.shape[-1]), int(top_boxes.shape[-1]), cls_preds.device

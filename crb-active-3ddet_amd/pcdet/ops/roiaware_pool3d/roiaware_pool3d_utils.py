@@ -75,6 +75,16 @@ class RoIAwarePool3dFunction(Function):
         pts_idx, argmax, method, P, C, (ox, oy, oz), mp = ctx.roiaware_pool3d_for_backward
         g = grad_out.contiguous().float()
         grad_in = torch.zeros((P, C), dtype=torch.float32, device=g.device)
+        if method == 0 and torch.are_deterministic_algorithms_enabled():
+            # the launch below adds with float atomics, in arrival order: a point that is the maximum of cells of several RoIs gets
+            # its sum in an order that changes from call to call. Under the flag: torch's sorted accumulate (the max method is what
+            # carries gradients on the DISABLE_PART route, whose avg side pools coordinates). The same sums in another order; the
+            # boolean-mask gather below reads its row count back (a host synchronisation the atomic launch does not have)
+            am = argmax.view(-1, C).long()
+            hit = am >= 0
+            flat = (am * C + torch.arange(C, device=g.device))[hit]
+            grad_in.view(-1).index_put_((flat,), g.view(-1, C)[hit], accumulate=True)
+            return None, None, grad_in, None, None, None
         check(lib.crb_roiaware_pool3d_backward(pts_idx.shape[0], C, mp, ox, oy, oz, ptr(pts_idx), ptr(argmax), ptr(g),
                                                ptr(grad_in), method, cur_stream(g.device)),
               'crb_roiaware_pool3d_backward')

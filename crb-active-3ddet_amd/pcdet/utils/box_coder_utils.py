@@ -47,3 +47,50 @@ class ResidualCoder(object):
         if rest_e.shape[-1] > 0:
             parts.append(rest_e + rest_a)
         return torch.cat(parts, dim=-1)
+
+
+class PointResidualCoder(object):
+    """box codes relative to a point (box_coder_utils.py:144-221): offsets to the point, log dims, cos / sin of the heading.
+    use_mean_size: offsets and dims relative to the mean size of the box's class. mean_size is a host tensor here (the reference
+    calls .cuda() in the constructor); `anchor_sizes` moves it to where it is asked for, once per device and dtype."""
+    def __init__(self, code_size=8, use_mean_size=True, **kwargs):
+        super().__init__()
+        self.code_size = code_size
+        self.use_mean_size = use_mean_size
+        self._moved = {}
+        if self.use_mean_size:
+            self.mean_size = torch.tensor(kwargs['mean_size'], dtype=torch.float32)
+            assert self.mean_size.dim() == 2 and self.mean_size.shape[1] == 3 and self.mean_size.min() > 0
+
+    def anchor_sizes(self, like):
+        """mean_size (K,3) on the device and in the dtype of `like`"""
+        key = (like.device, like.dtype)
+        if key not in self._moved:
+            self._moved[key] = self.mean_size.to(device=like.device, dtype=like.dtype).contiguous()
+        return self._moved[key]
+
+    def encode_torch(self, gt_boxes, points, gt_classes=None):
+        """gt_boxes (N, 7 + C), points (N,3), gt_classes (N) in 1 .. K -> (N, 8 + C)"""
+        d = torch.clamp_min(gt_boxes[..., 3:6], 1e-5)
+        off = gt_boxes[..., 0:3] - points
+        if self.use_mean_size:
+            assert gt_classes.numel() == 0 or int(gt_classes.max()) <= self.mean_size.shape[0]
+            a = self.anchor_sizes(gt_boxes)[gt_classes - 1]
+            diagonal = torch.sqrt(a[..., 0:1] ** 2 + a[..., 1:2] ** 2)
+            off = torch.cat([off[..., 0:2] / diagonal, off[..., 2:3] / a[..., 2:3]], dim=-1)
+            d = d / a
+        rg = gt_boxes[..., 6:7]
+        return torch.cat([off, torch.log(d), torch.cos(rg), torch.sin(rg), gt_boxes[..., 7:]], dim=-1)
+
+    def decode_torch(self, box_encodings, points, pred_classes=None):
+        """box_encodings (N, 8 + C), points (N,3), pred_classes (N) in 1 .. K -> (N, 7 + C)"""
+        e = box_encodings
+        off, d = e[..., 0:3], torch.exp(e[..., 3:6])
+        if self.use_mean_size:
+            assert pred_classes.numel() == 0 or int(pred_classes.max()) <= self.mean_size.shape[0]
+            a = self.anchor_sizes(e)[pred_classes - 1]
+            diagonal = torch.sqrt(a[..., 0:1] ** 2 + a[..., 1:2] ** 2)
+            off = torch.cat([off[..., 0:2] * diagonal, off[..., 2:3] * a[..., 2:3]], dim=-1)
+            d = d * a
+        rg = torch.atan2(e[..., 7:8], e[..., 6:7])
+        return torch.cat([off + points, d, rg, e[..., 8:]], dim=-1)

@@ -887,6 +887,48 @@ int crb_part_loss_backward(const float* d_cls, const float* d_part, const float*
                            float* grad_part, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * box branch of the point heads: PointIntraPartOffsetHead with TARGET_CONFIG.BOX_CODER (PartA2_free.yaml) and PointHeadBox
+ * (csrc/point_box.hip)
+ * crb_point_box_targets is crb_part_targets (same inputs, the same bits in labels, owner and part_labels) plus
+ *   PointResidualCoder.encode_torch with use_mean_size (pcdet/utils/box_coder_utils.py:153-187) of every owned point, in one launch:
+ *   mean_size (K,3) f32 on the device -> box_labels (N,8) f32 = {(xg - xa) / sqrt(dxa^2 + dya^2), (yg - ya) / the same, (zg - za) / dza,
+ *   log(dxg / dxa), log(dyg / dya), log(dzg / dza), cos rz, sin rz} with the gt dims clamped at 1e-5 and (dxa, dya, dza) =
+ *   mean_size[class - 1] of the ground truth's CLASS COLUMN (also when num_class == 1 labels the point 1), formed in f64 and rounded
+ *   once; zeros on every row without an owner. A class column outside 1 .. K is clamped into it (the reference asserts; the class
+ *   column lives on the device and reading it back would be the host sync this launch removes). part_labels may be NULL
+ *   (PointHeadBox: no part branch), then it is not written.
+ * crb_point_box_loss_forward is crb_part_loss_forward plus get_box_layer_loss (point_head_template.py:175-195) with
+ *   WeightedSmoothL1Loss (pcdet/utils/loss_utils.py:75-134): box_preds, box_labels (n,8); code_weights: 8 HOST floats; beta: f64, as the reference's Python float; a NaN label is
+ *   replaced by the prediction (a zero term, a zero gradient); diff * code_weight; 0.5 d^2 / beta below beta, |d| - beta / 2 above, |d|
+ *   when beta < 1e-5; rows with label > 0 weigh 1 / max(pos,1), the others 0 -> loss (4) f64 = {point_loss_cls, point_loss_part,
+ *   point_loss_box = box_weight * sum over rows and codes, pos}; d_cls (n,C), d_part (n,3), d_box (n,8) for unit upstream values.
+ *   part_preds NULL switches the part term off (point_loss_part = 0, d_part untouched). Two launches over cdiv(n,1024) workgroups, the
+ *   partials are four f64 sums per tile, every workgroup adds them in one fixed order, no atomics: bit-identical from call to call.
+ *   workspace: crb_point_box_loss_workspace_bytes(n), uninitialised.
+ * crb_point_box_loss_backward: grad_losses (3) f32 on the device = upstream gradients of the three losses -> grad_x = d_x *
+ *   grad_losses[k]. d_part / grad_part NULL: no part branch. One launch, no host read-back.
+ * crb_point_box_decode replaces generate_predicted_boxes (point_head_template.py:197-211) + PointResidualCoder.decode_torch
+ *   (box_coder_utils.py:189-221) and the per-frame packing of RoIHeadTemplate.proposal_layer: cls_preds (N,C), box_preds (N,8), points
+ *   (N,4) frame-sorted, frame_offsets (B+1) i32 -> batch_cls_preds (B,amax,C): the rows' logits, -inf past a frame's count;
+ *   batch_box_preds (B,amax,7): decoded with mean_size[argmax class (first maximum)] (C <= K), rz = atan2(sin, cos), formed in f64
+ *   and rounded once, zeros past the count; counts (B) i32 = rows of the frame. amax: the caller's bound on a frame's rows: rows beyond it
+ *   are dropped, and counts[b] > amax is how the caller can tell. One launch.
+ * ---------------------------------------------------------------------------------------------- */
+int crb_point_box_targets(const float* points, const int32_t* frame_offsets, const float* gt_boxes, int B, int64_t N, int G,
+                          const float* extra_width, int num_class, const float* mean_size, int K, int64_t* labels, int32_t* owner,
+                          float* box_labels, float* part_labels, void* stream);
+int64_t crb_point_box_loss_workspace_bytes(int64_t n);
+int crb_point_box_loss_forward(const float* cls_preds, const float* part_preds, const float* box_preds, const int64_t* labels,
+                               const float* part_labels, const float* box_labels, int64_t n, int C, float alpha, float gamma,
+                               const float* code_weights, double beta, float cls_weight, float part_weight, float box_weight, double* loss,
+                               float* d_cls, float* d_part, float* d_box, void* workspace, int64_t workspace_bytes, void* stream);
+int crb_point_box_loss_backward(const float* d_cls, const float* d_part, const float* d_box, const float* grad_losses, int64_t n, int C,
+                                float* grad_cls, float* grad_part, float* grad_box, void* stream);
+int crb_point_box_decode(const float* points, const int32_t* frame_offsets, const float* cls_preds, const float* box_preds,
+                         const float* mean_size, int B, int64_t N, int amax, int C, int K, float* batch_cls_preds, float* batch_box_preds,
+                         int32_t* counts, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * a22 / a24  second-stage losses and the canonical transformation of the sampled ground truths (csrc/rcnn_loss.hip)
  * replaces: RoIHeadTemplate.get_box_cls_layer_loss (BinaryCrossEntropy; pcdet/models/roi_heads/roi_head_template.py:261-285),
  *           get_box_reg_layer_loss (smooth-l1 + CORNER_LOSS_REGULARIZATION, the branch without reg_sample_targets; :142-259) with
