@@ -1581,7 +1581,7 @@ static inline int64_t bqg_buckets(int64_t n_total) {
   return nb;
 }
 extern "C" int64_t crb_ball_query2_grid_workspace_bytes(int64_t n_total) {
-  if (n_total <= 0) return 256;
+  if (n_total < 0) n_total = 0;       // a call without points still clears the counts and lays out cursors, tiles and prefixes
   const int64_t nb = bqg_buckets(n_total);
   return 4 * (crb_align_up(nb + 1, 64) + crb_align_up(nb, 64) + 2 * crb_align_up(n_total, 64) + crb_align_up(crb_scan_num_tiles(nb + 1), 64) + 2 * 4096 + 128) + 1024;
 }
