@@ -332,11 +332,39 @@ def pv_rcnn_cfg(kind='kitti'):
     })
 
 
-def pv_rcnn_plusplus_cfg(kind='kitti'):
+def _vector_pool(kind, reduced, msg, groups, **extra):
+    """one VectorPoolAggregationModuleMSG section; groups: (NUM_LOCAL_VOXEL, MAX_NEIGHBOR_DISTANCE, NEIGHBOR_NSAMPLE, POST_MLPS)"""
+    d = dict(extra)
+    d.update({'NAME': 'VectorPoolAggregationModuleMSG', 'NUM_GROUPS': len(groups), 'LOCAL_AGGREGATION_TYPE': kind,
+              'NUM_REDUCED_CHANNELS': reduced, 'NUM_CHANNELS_OF_LOCAL_AGGREGATION': 32, 'MSG_POST_MLPS': list(msg)})
+    for k, (grid, dist, nsample, post) in enumerate(groups):
+        d['GROUP_CFG_%d' % k] = {'NUM_LOCAL_VOXEL': list(grid), 'MAX_NEIGHBOR_DISTANCE': dist, 'NEIGHBOR_NSAMPLE': nsample,
+                                 'POST_MLPS': list(post)}
+    return d
+
+
+def pv_rcnn_plusplus_vector_pool_sections(raw_reduced=2):
+    """the four VectorPoolAggregationModuleMSG sections of tools/cfgs/waymo_models/pv_rcnn_plusplus.yaml: SA_LAYER raw_points /
+    x_conv3 / x_conv4 (local_interpolation) and ROI_GRID_POOL (voxel_random_choice)"""
+    g3 = (3, 3, 3)
+    sa = {'raw_points': _vector_pool('local_interpolation', raw_reduced, [32], [((2, 2, 2), 0.2, -1, (32, 32)), (g3, 0.4, -1, (32, 32))],
+                                     FILTER_NEIGHBOR_WITH_ROI=True, RADIUS_OF_NEIGHBOR_WITH_ROI=2.4),
+          'x_conv3': _vector_pool('local_interpolation', 32, [128], [(g3, 1.2, -1, (64, 64)), (g3, 2.4, -1, (64, 64))], DOWNSAMPLE_FACTOR=4,
+                                  INPUT_CHANNELS=64, FILTER_NEIGHBOR_WITH_ROI=True, RADIUS_OF_NEIGHBOR_WITH_ROI=4.0),
+          'x_conv4': _vector_pool('local_interpolation', 32, [128], [(g3, 2.4, -1, (64, 64)), (g3, 4.8, -1, (64, 64))], DOWNSAMPLE_FACTOR=8,
+                                  INPUT_CHANNELS=64, FILTER_NEIGHBOR_WITH_ROI=True, RADIUS_OF_NEIGHBOR_WITH_ROI=6.4)}
+    pool = _vector_pool('voxel_random_choice', 30, [128], [(g3, 0.8, 32, (64, 64)), (g3, 1.6, 32, (64, 64))], GRID_SIZE=6)
+    return sa, pool
+
+
+def pv_rcnn_plusplus_cfg(kind='kitti', aggregation='sa'):
     """pv_rcnn_cfg(kind) with the PFE section and the RoI-head NMS sizes of tools/cfgs/waymo_models/pv_rcnn_plusplus.yaml: keypoints by
     sectorized proposal-centric sampling (SPC, 6 sectors, 1.6 m around the proposals), feature sources bev / x_conv3 / x_conv4 /
-    raw_points with their neighbours filtered by the RoIs (2.4 / 4.0 / 6.4 m), 90 fused features, 100 test RoIs. The set-abstraction
-    layers and the RoI grid pool stay PV-RCNN's StackSAModuleMSG: the yaml's VectorPoolAggregationModuleMSG is not ported."""
+    raw_points with their neighbours filtered by the RoIs (2.4 / 4.0 / 6.4 m), 90 fused features, 100 test RoIs.
+    aggregation='sa' (the default): the set-abstraction layers and the RoI grid pool are PV-RCNN's StackSAModuleMSG.
+    aggregation='vector_pool': the yaml's four VectorPoolAggregationModuleMSG sections as they stand there; kind='kitti' reduces the
+    raw points to 1 channel instead of 2 (KITTI clouds carry one feature, and the layer asserts divisibility)."""
+    assert aggregation in ('sa', 'vector_pool')
     c = pv_rcnn_cfg(kind)
     m = c.MODEL
     m.NAME = 'PVRCNNPlusPlus'
@@ -348,6 +376,10 @@ def pv_rcnn_plusplus_cfg(kind='kitti'):
         m.PFE.SA_LAYER[src].update({'FILTER_NEIGHBOR_WITH_ROI': True, 'RADIUS_OF_NEIGHBOR_WITH_ROI': radius})
     for src in ('x_conv1', 'x_conv2'):
         m.PFE.SA_LAYER.pop(src)
+    if aggregation == 'vector_pool':
+        sa, pool = pv_rcnn_plusplus_vector_pool_sections(raw_reduced=1 if kind == 'kitti' else 2)
+        m.PFE.SA_LAYER = EasyDict(sa)
+        m.ROI_HEAD.ROI_GRID_POOL = EasyDict(pool)
     m.ROI_HEAD.pop('SAMPLING_ROUND', None)
     m.ROI_HEAD.NMS_CONFIG.TRAIN.update({'NMS_PRE_MAXSIZE': 9000, 'NMS_POST_MAXSIZE': 512, 'NMS_THRESH': 0.8})
     m.ROI_HEAD.NMS_CONFIG.TEST.update({'NMS_PRE_MAXSIZE': 1024, 'NMS_POST_MAXSIZE': 100, 'NMS_THRESH': 0.7, 'SCORE_THRESH': 0.1})

@@ -2,8 +2,8 @@
 proposals (PFE.SAMPLE_METHOD SPC, crbhip/spc.py). The proposal layer therefore runs BEFORE the PFE, and in training the RoI sampler
 too: the PFE sees the sampled rois. RoIHeadTemplate.proposal_layer returns early when `rois` exist and PVRCNNHead.forward takes
 batch_dict['roi_targets_dict'], so the RoI head itself is PV-RCNN's.
-The set-abstraction layers and the RoI grid pool are StackSAModuleMSG here (pcdet.model_cfgs.pv_rcnn_plusplus_cfg); the reference
-yaml's VectorPoolAggregationModuleMSG needs ops this port does not have yet and raises where the layer is built.
+The set-abstraction layers and the RoI grid pool are StackSAModuleMSG by default (pcdet.model_cfgs.pv_rcnn_plusplus_cfg);
+aggregation='vector_pool' there installs the reference yaml's VectorPoolAggregationModuleMSG sections (csrc/vector_pool.hip).
 Not supported on this detector: the LLAL loss net (its per-frame point loss reshapes by NUM_KEYPOINTS, which SPC does not keep)."""
 from .pv_rcnn import PVRCNN
 

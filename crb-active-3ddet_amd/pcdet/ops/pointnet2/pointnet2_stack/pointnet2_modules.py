@@ -1,5 +1,7 @@
 """StackSAModuleMSG / build_local_aggregation_module (pointnet2_modules.py:10-112): multi-scale set abstraction on
-stacked batches: ball query + grouping (HIP) -> shared 1x1 MLP (+BN+ReLU) -> max over the neighbourhood."""
+stacked batches: ball query + grouping (HIP) -> shared 1x1 MLP (+BN+ReLU) -> max over the neighbourhood.
+VectorPoolLocalInterpolateModule / VectorPoolAggregationModule / VectorPoolAggregationModuleMSG (pointnet2_modules.py:160-470): per new
+point a grid of cells, per cell three-NN interpolation (or one picked point) -> grouped 1x1 convolution -> post MLPs (csrc/vector_pool.hip)."""
 from typing import List
 
 import torch
@@ -34,11 +36,24 @@ FUSED_GROUP = True     # one HIP launch builds the (1, 3+C, M, ns) MLP input (Fa
 FUSED_TRAIN = __import__('os').environ.get('CRB_SA_TRAIN_FUSED', '1') == '1'
 
 
+# VectorPool layers: the fused kernels of csrc/vector_pool.hip + the grouped 1x1 convolution as G batched GEMMs;
+# CRB_VECTOR_POOL_FUSED=0 = the reference's torch expressions on the same three-NN / voxel-query results (A/B, test reference)
+VECTOR_POOL_FUSED = __import__('os').environ.get('CRB_VECTOR_POOL_FUSED', '1') == '1'
+_VECTOR_POOL_KEYS = ('NUM_GROUPS', 'LOCAL_AGGREGATION_TYPE', 'NUM_CHANNELS_OF_LOCAL_AGGREGATION', 'MSG_POST_MLPS')
+
+
 def build_local_aggregation_module(input_channels, config):
     name = config.get('NAME', 'StackSAModuleMSG')
+    if name == 'VectorPoolAggregationModuleMSG':
+        missing = [k for k in _VECTOR_POOL_KEYS if k not in config]
+        missing += ['GROUP_CFG_%d' % k for k in range(int(config.get('NUM_GROUPS', 1))) if 'GROUP_CFG_%d' % k not in config]
+        if missing:
+            raise NotImplementedError('%s cannot be built from this section: it has no %s (a StackSAModuleMSG section with only its '
+                                      'NAME changed does not describe a vector_pool layer; pcdet.model_cfgs.pv_rcnn_plusplus_cfg(kind, '
+                                      "aggregation='vector_pool') installs complete ones)" % (name, ', '.join(missing)))
+        return VectorPoolAggregationModuleMSG(input_channels=input_channels, config=config), config.MSG_POST_MLPS[-1]
     if name != 'StackSAModuleMSG':
-        raise NotImplementedError(name + ' needs the vector_pool / three_nn_for_vector_pool ops, which this port does not have yet '
-                                         '(PV-RCNN++ runs with StackSAModuleMSG layers: pcdet.model_cfgs.pv_rcnn_plusplus_cfg)')
+        raise NotImplementedError(name)
     mlps = [[input_channels] + list(m) for m in config.MLPS]
     layer = StackSAModuleMSG(radii=config.POOL_RADIUS, nsamples=config.NSAMPLE, mlps=mlps, use_xyz=True,
                              pool_method='max_pool')
@@ -229,3 +244,247 @@ class StackSAModuleMSG(nn.Module):
                 raise NotImplementedError
             outs.append(x.squeeze(0).permute(1, 0))
         return new_xyz, torch.cat(outs, dim=1)
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------
+# VectorPool aggregation (reference: pointnet2_modules.py:160-470). Parameter and buffer names are the reference's.
+# ---------------------------------------------------------------------------------------------------------------------------------
+def _three_interpolate(features, idx, weight):
+    """features (N, C), idx (E, 3), weight (E, 3) -> (E, C): w0 f0 + w1 f1 + w2 f2"""
+    if features.is_cuda:
+        return pointnet2_utils.three_interpolate(features, idx, weight)
+    i = idx.long()
+    return weight[:, 0:1] * features[i[:, 0]] + weight[:, 1:2] * features[i[:, 1]] + weight[:, 2:3] * features[i[:, 2]]
+
+
+def _bn_relu_rows(bn, x):
+    """relu(bn(x)) on (M, C) rows; the fused row kernels where they cover the width"""
+    if x.is_cuda and bnrelu.supported(x, bn) and (not bn.training or bn.momentum is not None):
+        return bnrelu.bn_relu(x, bn, relu=True)
+    return F.relu(bn(x))
+
+
+def _conv1d_rows(seq, x):
+    """an nn.Sequential of Conv1d(k = 1, no bias) / BatchNorm1d / ReLU triples on (M, C) rows"""
+    mods = list(seq)
+    for i in range(0, len(mods), 3):
+        x = _bn_relu_rows(mods[i + 1], _LinearRows.apply(x, mods[i].weight.flatten(1)) if x.is_cuda else F.linear(x, mods[i].weight.flatten(1)))
+    return x
+
+
+class VectorPoolLocalInterpolateModule(nn.Module):
+    def __init__(self, mlp, num_voxels, max_neighbour_distance, nsample, neighbor_type, use_xyz=True,
+                 neighbour_distance_multiplier=1.0, xyz_encoding_type='concat'):
+        """neighbor_type 1: ball, others: cube; nsample: all (-1) or a limit (> 0)"""
+        super().__init__()
+        self.num_voxels = num_voxels
+        self.num_total_grids = self.num_voxels[0] * self.num_voxels[1] * self.num_voxels[2]
+        self.max_neighbour_distance = max_neighbour_distance
+        self.neighbor_distance_multiplier = neighbour_distance_multiplier
+        self.nsample = nsample
+        self.neighbor_type = neighbor_type
+        self.use_xyz = use_xyz
+        self.xyz_encoding_type = xyz_encoding_type
+        if self.use_xyz and self.xyz_encoding_type != 'concat':
+            raise NotImplementedError('xyz_encoding_type ' + str(xyz_encoding_type))
+        if mlp is not None:
+            mlp = list(mlp)
+            if self.use_xyz:
+                mlp[0] += 9
+            layers = []
+            for c_in, c_out in zip(mlp[:-1], mlp[1:]):
+                layers += [nn.Conv2d(c_in, c_out, kernel_size=1, bias=False), nn.BatchNorm2d(c_out), nn.ReLU()]
+            self.mlp = nn.Sequential(*layers)
+        else:
+            self.mlp = None
+        self.num_avg_length_of_neighbor_idxs = 1000        # (handed through the op and back: nothing is sized by it)
+
+    def three_nn(self, support_xyz, xyz_batch_cnt, new_xyz, new_xyz_grid_centers, new_xyz_batch_cnt):
+        with torch.no_grad():
+            dist, idx, _ = pointnet2_utils.three_nn_for_vector_pool_by_two_step(
+                support_xyz, xyz_batch_cnt, new_xyz, new_xyz_grid_centers, new_xyz_batch_cnt, self.max_neighbour_distance, self.nsample,
+                self.neighbor_type, self.num_avg_length_of_neighbor_idxs, self.num_total_grids, self.neighbor_distance_multiplier)
+        return dist, idx
+
+    def forward_cells(self, support_xyz, support_features, xyz_batch_cnt, new_xyz, new_xyz_grid_centers, new_xyz_batch_cnt):
+        """the fused route: -> (G, M, C + 9), cell-major, what the grouped convolution reads as G GEMMs"""
+        from crbhip import vector_pool
+        assert self.use_xyz and self.mlp is None
+        dist, idx = self.three_nn(support_xyz, xyz_batch_cnt, new_xyz, new_xyz_grid_centers, new_xyz_batch_cnt)
+        return vector_pool.interpolate(support_features, idx, dist, new_xyz_grid_centers.detach(), support_xyz.detach())
+
+    def forward(self, support_xyz, support_features, xyz_batch_cnt, new_xyz, new_xyz_grid_centers, new_xyz_batch_cnt):
+        """the reference's expressions: -> (M * G, C + 9) rows (C_out of the mlp when there is one)"""
+        dist, idx = self.three_nn(support_xyz, xyz_batch_cnt, new_xyz, new_xyz_grid_centers, new_xyz_batch_cnt)
+        M, G = idx.shape[0], idx.shape[1]
+        dist_recip = 1.0 / (dist + 1e-8)
+        norm = torch.sum(dist_recip, dim=-1, keepdim=True)
+        weight = dist_recip / torch.clamp_min(norm, min=1e-8)
+        idx = idx.view(-1, 3)
+        empty_mask = idx[:, 0] == -1
+        idx = torch.where(empty_mask[:, None], torch.zeros_like(idx), idx)
+        if support_features.shape[0] == 0:                                      # (the reference reads row 0 for empty cells)
+            width = support_features.shape[1] + (9 if self.use_xyz else 0)
+            new_features = support_features.new_zeros((M * G, width))
+        else:
+            new_features = _three_interpolate(support_features, idx, weight.view(-1, 3))
+            if self.use_xyz:
+                near = support_xyz[idx.long()].view(-1, 3, 3)
+                local_xyz = (new_xyz_grid_centers.view(-1, 1, 3) - near).view(-1, 9)
+                new_features = torch.cat((new_features, local_xyz), dim=-1)
+            new_features = new_features.masked_fill(empty_mask[:, None], 0)
+        if self.mlp is not None:
+            new_features = self.mlp(new_features.permute(1, 0)[None, :, :, None])
+            new_features = new_features.squeeze(dim=0).squeeze(dim=-1).permute(1, 0)
+        return new_features
+
+
+class VectorPoolAggregationModule(nn.Module):
+    def __init__(self, input_channels, num_local_voxel=(3, 3, 3), local_aggregation_type='local_interpolation',
+                 num_reduced_channels=30, num_channels_of_local_aggregation=32, post_mlps=(128,),
+                 max_neighbor_distance=None, neighbor_nsample=-1, neighbor_type=0, neighbor_distance_multiplier=2.0):
+        super().__init__()
+        self.num_local_voxel = num_local_voxel
+        self.total_voxels = self.num_local_voxel[0] * self.num_local_voxel[1] * self.num_local_voxel[2]
+        self.local_aggregation_type = local_aggregation_type
+        assert self.local_aggregation_type in ['local_interpolation', 'voxel_avg_pool', 'voxel_random_choice']
+        if self.local_aggregation_type == 'voxel_avg_pool':
+            raise NotImplementedError('LOCAL_AGGREGATION_TYPE voxel_avg_pool is not built (local_interpolation and '
+                                      'voxel_random_choice are)')
+        self.input_channels = input_channels
+        self.num_reduced_channels = input_channels if num_reduced_channels is None else num_reduced_channels
+        self.num_channels_of_local_aggregation = num_channels_of_local_aggregation
+        self.max_neighbour_distance = max_neighbor_distance
+        self.neighbor_nsample = neighbor_nsample
+        self.neighbor_type = neighbor_type
+        if self.local_aggregation_type == 'local_interpolation':
+            self.local_interpolate_module = VectorPoolLocalInterpolateModule(
+                mlp=None, num_voxels=self.num_local_voxel, max_neighbour_distance=self.max_neighbour_distance,
+                nsample=self.neighbor_nsample, neighbor_type=self.neighbor_type,
+                neighbour_distance_multiplier=neighbor_distance_multiplier)
+            num_c_in = (self.num_reduced_channels + 9) * self.total_voxels
+        else:
+            self.local_interpolate_module = None
+            num_c_in = (self.num_reduced_channels + 3) * self.total_voxels
+        num_c_out = self.total_voxels * self.num_channels_of_local_aggregation
+        self.separate_local_aggregation_layer = nn.Sequential(
+            nn.Conv1d(num_c_in, num_c_out, kernel_size=1, groups=self.total_voxels, bias=False), nn.BatchNorm1d(num_c_out), nn.ReLU())
+        layers, c_in = [], num_c_out
+        for c in post_mlps:
+            layers += [nn.Conv1d(c_in, c, kernel_size=1, bias=False), nn.BatchNorm1d(c), nn.ReLU()]
+            c_in = c
+        self.post_mlps = nn.Sequential(*layers)
+        self.num_mean_points_per_grid = 20                 # (handed through the op and back: nothing is sized by it)
+        self.init_weights()
+
+    def init_weights(self):
+        for m in self.modules():
+            if isinstance(m, nn.Conv2d) or isinstance(m, nn.Conv1d):
+                nn.init.kaiming_normal_(m.weight)
+                if m.bias is not None:
+                    nn.init.constant_(m.bias, 0)
+            if isinstance(m, nn.BatchNorm2d) or isinstance(m, nn.BatchNorm1d):
+                nn.init.constant_(m.weight, 1.0)
+                nn.init.constant_(m.bias, 0)
+
+    def extra_repr(self) -> str:
+        return f'radius={self.max_neighbour_distance}, local_voxels=({self.num_local_voxel}, ' \
+               f'local_aggregation_type={self.local_aggregation_type}, ' \
+               f'num_c_reduction={self.input_channels}->{self.num_reduced_channels}, ' \
+               f'num_c_local_aggregation={self.num_channels_of_local_aggregation}'
+
+    def vector_pool_with_voxel_query(self, xyz, xyz_batch_cnt, features, new_xyz, new_xyz_batch_cnt):
+        """-> (M, G, 3 + C) [local xyz, features] per cell, point_cnt_of_grid (M, G)"""
+        new_features, new_local_xyz, _, point_cnt_of_grid = pointnet2_utils.vector_pool_with_voxel_query_op(
+            xyz, xyz_batch_cnt, features, new_xyz, new_xyz_batch_cnt, self.num_local_voxel[0], self.num_local_voxel[1],
+            self.num_local_voxel[2], self.max_neighbour_distance, self.num_reduced_channels, 1, self.num_mean_points_per_grid,
+            self.neighbor_nsample, self.neighbor_type, 1)
+        M = new_features.shape[0]
+        cells = torch.cat((new_local_xyz.view(M, -1, 3), new_features.view(M, -1, self.num_reduced_channels)), dim=-1)
+        return cells, point_cnt_of_grid
+
+    @staticmethod
+    def get_dense_voxels_by_center(point_centers, max_neighbour_distance, num_voxels):
+        """point_centers (N, 3) -> voxel centres (N, total_voxels, 3), z fastest"""
+        R = max_neighbour_distance
+        device = point_centers.device
+        x_grids = torch.arange(-R + R / num_voxels[0], R - R / num_voxels[0] + 1e-5, 2 * R / num_voxels[0], device=device)
+        y_grids = torch.arange(-R + R / num_voxels[1], R - R / num_voxels[1] + 1e-5, 2 * R / num_voxels[1], device=device)
+        z_grids = torch.arange(-R + R / num_voxels[2], R - R / num_voxels[2] + 1e-5, 2 * R / num_voxels[2], device=device)
+        x_offset, y_offset, z_offset = torch.meshgrid(x_grids, y_grids, z_grids, indexing='ij')
+        xyz_offset = torch.cat((x_offset.contiguous().view(-1, 1), y_offset.contiguous().view(-1, 1),
+                                z_offset.contiguous().view(-1, 1)), dim=-1)
+        return point_centers[:, None, :] + xyz_offset[None, :, :]
+
+    def vector_pool_with_local_interpolate(self, xyz, xyz_batch_cnt, features, new_xyz, new_xyz_batch_cnt):
+        """-> (M, total_voxels * (C + 9)), the reference's expressions"""
+        voxel_centers = self.get_dense_voxels_by_center(new_xyz, self.max_neighbour_distance, self.num_local_voxel)
+        voxel_features = self.local_interpolate_module.forward(
+            support_xyz=xyz, support_features=features, xyz_batch_cnt=xyz_batch_cnt, new_xyz=new_xyz,
+            new_xyz_grid_centers=voxel_centers, new_xyz_batch_cnt=new_xyz_batch_cnt)
+        return voxel_features.contiguous().view(-1, self.total_voxels * voxel_features.shape[-1])
+
+    def forward(self, xyz, xyz_batch_cnt, new_xyz, new_xyz_batch_cnt, features, **kwargs):
+        """xyz (N, 3), features (N, C), new_xyz (M, 3) -> new_xyz, new_features (M, post_mlps[-1])"""
+        N, C = features.shape
+        assert C % self.num_reduced_channels == 0, \
+            f'the input channels ({C}) should be an integral multiple of num_reduced_channels({self.num_reduced_channels})'
+        features = features.view(N, C // self.num_reduced_channels, self.num_reduced_channels).sum(dim=1)   # (N = 0 is legal)
+        interp =self.local_aggregation_type == 'local_interpolation'
+        if VECTOR_POOL_FUSED and xyz.is_cuda and not bnrelu.frame_groups_active():
+            G, M = self.total_voxels, new_xyz.shape[0]
+            if interp:
+                centers = self.get_dense_voxels_by_center(new_xyz, self.max_neighbour_distance, self.num_local_voxel)
+                cells = self.local_interpolate_module.forward_cells(xyz, features, xyz_batch_cnt, new_xyz, centers.contiguous(),
+                                                                    new_xyz_batch_cnt)              # (G, M, C + 9)
+            else:
+                cells = self.vector_pool_with_voxel_query(xyz, xyz_batch_cnt, features, new_xyz, new_xyz_batch_cnt)[0].transpose(0, 1)
+            conv, bn = self.separate_local_aggregation_layer[0], self.separate_local_aggregation_layer[1]
+            w = conv.weight.view(G, self.num_channels_of_local_aggregation, -1)       # (G * 32, C + 9, 1): the G GEMM operands
+            rows = torch.bmm(cells, w.transpose(1, 2)).permute(1, 0, 2).reshape(M, -1)   # (M, G * 32), the conv's channel order
+            return new_xyz, _conv1d_rows(self.post_mlps, _bn_relu_rows(bn, rows))
+        if interp:
+            vector_features = self.vector_pool_with_local_interpolate(xyz, xyz_batch_cnt, features, new_xyz, new_xyz_batch_cnt)
+        else:
+            cells, _ = self.vector_pool_with_voxel_query(xyz, xyz_batch_cnt, features, new_xyz, new_xyz_batch_cnt)
+            vector_features = cells.reshape(cells.shape[0], -1)
+        vector_features = vector_features.permute(1, 0)[None, :, :]                # (1, G * C', M)
+        new_features = self.post_mlps(self.separate_local_aggregation_layer(vector_features))
+        return new_xyz, new_features.squeeze(dim=0).permute(1, 0)
+
+
+class VectorPoolAggregationModuleMSG(nn.Module):
+    def __init__(self, input_channels, config):
+        super().__init__()
+        self.model_cfg = config
+        self.num_groups = self.model_cfg.NUM_GROUPS
+        self.layers = []
+        c_in = 0
+        for k in range(self.num_groups):
+            cur = self.model_cfg[f'GROUP_CFG_{k}']
+            layer = VectorPoolAggregationModule(
+                input_channels=input_channels, num_local_voxel=cur.NUM_LOCAL_VOXEL, post_mlps=cur.POST_MLPS,
+                max_neighbor_distance=cur.MAX_NEIGHBOR_DISTANCE, neighbor_nsample=cur.NEIGHBOR_NSAMPLE,
+                local_aggregation_type=self.model_cfg.LOCAL_AGGREGATION_TYPE,
+                num_reduced_channels=self.model_cfg.get('NUM_REDUCED_CHANNELS', None),
+                num_channels_of_local_aggregation=self.model_cfg.NUM_CHANNELS_OF_LOCAL_AGGREGATION, neighbor_distance_multiplier=2.0)
+            self.__setattr__(f'layer_{k}', layer)
+            c_in += cur.POST_MLPS[-1]
+        c_in += 3                                          # the new points' xyz
+        layers = []
+        for c in self.model_cfg.MSG_POST_MLPS:
+            layers += [nn.Conv1d(c_in, c, kernel_size=1, bias=False), nn.BatchNorm1d(c), nn.ReLU()]
+            c_in = c
+        self.msg_post_mlps = nn.Sequential(*layers)
+
+    def forward(self, **kwargs):
+        """xyz, xyz_batch_cnt, new_xyz, new_xyz_batch_cnt, features; other keywords (PVRCNNHead's query_group) are ignored"""
+        outs = []
+        for k in range(self.num_groups):
+            cur_xyz, cur_features = self.__getattr__(f'layer_{k}')(**kwargs)
+            outs.append(cur_features)
+        features = torch.cat([cur_xyz] + outs, dim=-1)
+        if VECTOR_POOL_FUSED and features.is_cuda and not bnrelu.frame_groups_active():
+            return cur_xyz, _conv1d_rows(self.msg_post_mlps, features)
+        new_features = self.msg_post_mlps(features.permute(1, 0)[None, :, :])
+        return cur_xyz, new_features.squeeze(dim=0).permute(1, 0)

@@ -1,6 +1,7 @@
 """pcdet.ops.pointnet2.pointnet2_stack.pointnet2_utils (reference: pointnet2_utils.py:8-299) over csrc/pointnet2_stack.hip.
 Same callables: ball_query, grouping_operation, QueryAndGroup, farthest_point_sample, stack_farthest_point_sample,
-three_nn, three_interpolate."""
+three_nn, three_interpolate; three_nn_for_vector_pool_by_two_step and vector_pool_with_voxel_query_op (reference: :302-448) over
+csrc/vector_pool.hip."""
 import ctypes
 
 import math
@@ -722,3 +723,159 @@ class ThreeInterpolate(Function):
 
 
 three_interpolate = ThreeInterpolate.apply
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------
+# VectorPool aggregation (reference: pointnet2_utils.py:302-448 over vector_pool_gpu.cu). Device tensors: csrc/vector_pool.hip
+# (crbhip.vector_pool); host tensors: the torch expressions below, the same results. Nothing is sized by the average neighbour-list
+# length / mean points per grid any more (there is no list): both ops hand back the value they were given.
+# ---------------------------------------------------------------------------------------------------------------------------------
+VP_MAX_CANDIDATES = 1000          # the reference's temp_idxs[1000]: later in-range points are ignored even if nearer
+
+
+def _vp_frames(xyz_batch_cnt, new_xyz_batch_cnt, N, M):
+    """-> [(first support row, support rows, first new row, end new row)]: the reference kernels' frame walk (a new point past the sum
+    of new_xyz_batch_cnt belongs to the last frame), support rows clamped to the array"""
+    a, b = [int(v) for v in xyz_batch_cnt.tolist()], [int(v) for v in new_xyz_batch_cnt.tolist()]
+    assert len(a) == len(b) and (len(a) > 0 or M == 0)
+    out, s, lo = [], 0, 0
+    for k in range(len(a)):
+        hi = M if k == len(a) - 1 else min(max(lo + b[k], lo), M)
+        start = min(max(s, 0), N)
+        out.append((start, min(max(a[k], 0), N - start), lo, hi))
+        s, lo = s + a[k], hi
+    return out
+
+
+def _vp_keep(local, dist, neighbor_type):
+    """local (m, n, 3) f32, dist a 0-dim f32 tensor -> (m, n) bool: the reference's range test (points on the face / sphere stay)"""
+    if neighbor_type == 1:
+        lx, ly, lz = local.unbind(-1)
+        return ~((lx * lx + ly * ly + lz * lz) > dist * dist)
+    return ~((local.abs() > dist).any(-1))
+
+
+def three_nn_for_vector_pool_torch(support_xyz, xyz_batch_cnt, new_xyz, new_xyz_grid_centers, new_xyz_batch_cnt, query_dist, nsample,
+                                   neighbor_type):
+    """-> idx (M, G, 3) i32, dist (M, G, 3) f32. The strict-< insertion of the reference kernel keeps the three smallest distances with
+    ties to the lower row: the first three of a stable ascending sort."""
+    support_xyz, new_xyz, centers = support_xyz.float(), new_xyz.float(), new_xyz_grid_centers.float()
+    M, G = int(centers.shape[0]), int(centers.shape[1])
+    inf = float('inf')
+    idx = torch.full((M, G, 3), -1, dtype=torch.int32, device=new_xyz.device)
+    dist = torch.full((M, G, 3), inf, dtype=torch.float32, device=new_xyz.device)
+    cap = nsample if 0 < nsample < VP_MAX_CANDIDATES else VP_MAX_CANDIDATES
+    qd = torch.tensor(float(query_dist), dtype=torch.float32, device=new_xyz.device)
+    for s, n, lo, hi in _vp_frames(xyz_batch_cnt, new_xyz_batch_cnt, int(support_xyz.shape[0]), M):
+        if n == 0 or hi <= lo:
+            continue
+        p = support_xyz[s:s + n]
+        step = max(1, (1 << 22) // (G * n))
+        for c0 in range(lo, hi, step):
+            c1 = min(c0 + step, hi)
+            keep = _vp_keep(p[None, :, :] - new_xyz[c0:c1, None, :], qd, neighbor_type)
+            keep &= keep.long().cumsum(1) <= cap
+            c = centers[c0:c1]
+            dx, dy, dz = (c[:, :, None, a] - p[None, None, :, a] for a in range(3))
+            d = dx * dx + dy * dy + dz * dz
+            d = torch.where(keep[:, None, :], d, torch.full_like(d, inf))
+            val, order = torch.sort(d, dim=-1, stable=True)
+            val, order = val[..., :3], order[..., :3]
+            if n < 3:
+                val = torch.cat([val, val.new_full(val.shape[:2] + (3 - n,), inf)], -1)
+                order = torch.cat([order, order.new_zeros(order.shape[:2] + (3 - n,))], -1)
+            ok = val < inf
+            i = torch.where(ok, order + s, torch.full_like(order, -1))
+            v = torch.where(ok, val, torch.full_like(val, inf))
+            i = torch.where(i < 0, i[..., :1], i)                      # missing second / third slots repeat the first pick
+            v = torch.where(ok, v, v[..., :1])
+            # (the square root through f64: correctly rounded like the device's sqrtf; the host's vectorised f32 sqrt is not)
+            idx[c0:c1], dist[c0:c1] = i.to(torch.int32), v.double().sqrt().float()
+    return idx, dist
+
+
+def three_nn_for_vector_pool_by_two_step(support_xyz, xyz_batch_cnt, new_xyz, new_xyz_grid_centers, new_xyz_batch_cnt,
+                                         max_neighbour_distance, nsample, neighbor_type, avg_length_of_neighbor_idxs, num_total_grids,
+                                         neighbor_distance_multiplier):
+    """the reference's argument list -> (dist (M, G, 3), idx (M, G, 3) i32, torch.tensor(avg_length_of_neighbor_idxs)).
+    Query distance = neighbor_distance_multiplier * max_neighbour_distance around new_xyz (not around the grid centre)."""
+    assert new_xyz_grid_centers.dim() == 3 and new_xyz_grid_centers.shape[1] == num_total_grids
+    query = max_neighbour_distance * neighbor_distance_multiplier
+    if new_xyz.is_cuda:
+        from crbhip import vector_pool
+        idx, dist = vector_pool.three_nn(support_xyz.detach(), xyz_batch_cnt, new_xyz.detach(), new_xyz_grid_centers.detach(),
+                                         new_xyz_batch_cnt, query, nsample, neighbor_type)
+    else:
+        with torch.no_grad():
+            idx, dist = three_nn_for_vector_pool_torch(support_xyz, xyz_batch_cnt, new_xyz, new_xyz_grid_centers, new_xyz_batch_cnt,
+                                                       query, nsample, neighbor_type)
+    return dist, idx, torch.tensor(avg_length_of_neighbor_idxs)
+
+
+def vector_pool_voxel_torch(support_xyz, xyz_batch_cnt, support_features, new_xyz, new_xyz_batch_cnt, num_grid, max_distance, nsample,
+                            neighbor_type):
+    """voxel_random_choice as torch expressions -> new_features (M, G C), new_local_xyz (M, 3 G), point_cnt (M, G) i32, pick (M, G) i32.
+    The sequential scan fills a cell with the first in-range point that reaches it and stops after `limit` filled cells: the cells
+    whose first point is among the `limit` earliest."""
+    gx, gy, gz = (int(v) for v in num_grid)
+    G = gx * gy * gz
+    support_xyz, new_xyz = support_xyz.float(), new_xyz.float()
+    M, C, dev = int(new_xyz.shape[0]), int(support_features.shape[1]), new_xyz.device
+    R = torch.tensor(float(max_distance), dtype=torch.float32, device=dev)
+    sx, sy, sz = (R * 2 / n for n in (gx, gy, gz))
+    limit = nsample if 0 < nsample < G else G
+    feats, locs, picks = [], [], []
+    for s, n, lo, hi in _vp_frames(xyz_batch_cnt, new_xyz_batch_cnt, int(support_xyz.shape[0]), M):
+        m = hi - lo
+        if m <= 0:
+            continue
+        if n == 0:
+            feats.append(support_features.new_zeros((m, G, C)))
+            locs.append(new_xyz.new_zeros((m, G, 3)))
+            picks.append(torch.full((m, G), -1, dtype=torch.int64, device=dev))
+            continue
+        p, q = support_xyz[s:s + n], new_xyz[lo:hi]
+        local = p[None, :, :] - q[:, None, :]                              # (m, n, 3)
+        keep = _vp_keep(local, R, neighbor_type)
+        ix, iy, iz = (torch.floor((local[..., a] + R) / g).long() for a, g in enumerate((sx, sy, sz)))
+        cell = (ix * gy * gz + iy * gz + iz).clamp(0, G - 1)
+        first = torch.full((m, G + 1), n, dtype=torch.int64, device=dev)
+        first.scatter_reduce_(1, torch.where(keep, cell, torch.full_like(cell, G)), torch.arange(n, device=dev).expand(m, n), 'amin')
+        first = first[:, :G]
+        kth = torch.sort(first, dim=1).values[:, limit - 1:limit]
+        filled = (first < n) & (first <= kth)
+        row = torch.where(filled, first, torch.zeros_like(first))
+        feats.append(torch.where(filled[:, :, None], support_features[s:s + n][row], support_features.new_zeros(())))
+        locs.append(torch.where(filled[:, :, None], p[row] - q[:, None, :], p.new_zeros(())))
+        picks.append(torch.where(filled, first + s, torch.full_like(first, -1)))
+    if not feats:
+        return (support_features.new_zeros((M, G * C)), new_xyz.new_zeros((M, 3 * G)), torch.zeros((M, G), dtype=torch.int32, device=dev),
+                torch.full((M, G), -1, dtype=torch.int32, device=dev))
+    pick = torch.cat(picks).to(torch.int32)
+    return torch.cat(feats).reshape(M, G * C), torch.cat(locs).reshape(M, 3 * G), (pick >= 0).to(torch.int32), pick
+
+
+def vector_pool_with_voxel_query_op(support_xyz, xyz_batch_cnt, support_features, new_xyz, new_xyz_batch_cnt, num_grid_x, num_grid_y,
+                                    num_grid_z, max_neighbour_distance, num_c_out_each_grid, use_xyz, num_mean_points_per_grid=100,
+                                    nsample=-1, neighbor_type=0, pooling_type=0):
+    """the reference's argument list -> (new_features (M, G C), new_local_xyz (M, 3 G), IntTensor([num_mean_points_per_grid]),
+    point_cnt_of_grid (M, G) i32). Built: pooling_type 1 (voxel_random_choice) with as many input channels as channels per cell."""
+    if pooling_type != 1:
+        raise NotImplementedError('vector_pool_with_voxel_query_op: pooling_type 0 (voxel_avg_pool) is not built; only 1 '
+                                  '(voxel_random_choice) is')
+    if support_features.shape[1] != num_c_out_each_grid:
+        raise NotImplementedError('vector_pool_with_voxel_query_op: num_c_in (%d) != num_c_out_each_grid (%d) is not built (the '
+                                  'module always reduces the channels first)' % (support_features.shape[1], num_c_out_each_grid))
+    grid = (num_grid_x, num_grid_y, num_grid_z)
+    if new_xyz.is_cuda:
+        from crbhip import vector_pool
+        new_features, new_local_xyz, cnt, _ = vector_pool.voxel_pool(support_features, support_xyz.detach(), xyz_batch_cnt,
+                                                                     new_xyz.detach(), new_xyz_batch_cnt, grid, max_neighbour_distance,
+                                                                     nsample, neighbor_type)
+    else:
+        new_features, new_local_xyz, cnt, _ = vector_pool_voxel_torch(support_xyz.detach(), xyz_batch_cnt, support_features,
+                                                                      new_xyz.detach(), new_xyz_batch_cnt, grid, max_neighbour_distance,
+                                                                      nsample, neighbor_type)
+    if not use_xyz:
+        new_local_xyz = torch.zeros_like(new_local_xyz)
+    return new_features, new_local_xyz.detach(), torch.Tensor([num_mean_points_per_grid]).int(), cnt

@@ -1632,6 +1632,46 @@ int crb_kitti_match_pr(const int64_t* gt_off, const int64_t* dt_off, const int64
                        const int32_t* combo_aos, int num_combos, int num_aos, const double* thresholds, const int32_t* num_thresholds,
                        uint32_t* asg_big, int32_t* counts, double* sim_part, double* result, void* stream);
 
+/* VectorPool aggregation of PV-RCNN++ (csrc/vector_pool.hip)
+ * replaces: query_stacked_local_neighbor_idxs + query_three_nn_by_stacked_local_idxs, vector_pool_kernel_stack (pooling_type 1) and
+ *           vector_pool_grad_kernel_stack (pointnet2_stack/src/vector_pool_gpu.cu) with the host loops around them
+ *           (ThreeNNForVectorPoolByTwoStep, VectorPoolWithVoxelQuery of pointnet2_utils.py:302-448), and three_interpolate, the
+ *           coordinate gather, the two cats, the mask write and the permute of VectorPoolLocalInterpolateModule.forward
+ *           (pointnet2_modules.py:212-238).
+ * No neighbour list, cursor, retry or read-back; no float atomics. Rows are stacked frame by frame: xyz_batch_cnt / new_xyz_batch_cnt
+ * (B) device i32. Frame of new point m: the reference's walk over new_xyz_batch_cnt (a point past the sum belongs to the last frame);
+ * the frame's support rows are clamped to [0, N). G = number of cells <= 64 (CRB_ERR_UNSUPPORTED above).
+ * crb_vector_pool_three_nn: local = support - new (f32); cube: dropped when any |local| > query_dist, ball (neighbor_type 1): when
+ *   lx^2 + ly^2 + lz^2 > query_dist^2. Candidates: the frame's kept points in ascending row order, at most nsample (when > 0) and at
+ *   most 1000. Per cell d = (cx-x)^2 + (cy-y)^2 + (cz-z)^2 (f32, that association), strict < against best1, best2, best3 in turn;
+ *   missing second / third slots repeat the first; none: idx -1, dist +inf. idx (M, G, 3) i32 global rows, dist (M, G, 3) = sqrtf(d).
+ * crb_vector_pool_interp_forward: out (G, M, C + 9): C channels w0 f0 + w1 f1 + w2 f2 with w_j = r_j / max(r0 + r1 + r2, 1e-8),
+ *   r_j = 1 / (dist_j + 1e-8), then centre - xyz[idx_j] for j = 0..2; cells with idx < 0 are zeros and read no row (N = 0 is legal).
+ *   Row indices are clamped to [0, N).
+ * crb_vector_pool_interp_backward: grad_out (G, M, C + 9) -> grad_features (N, C), every row written. sorted_rows (E = 3 M G) i32
+ *   ascending = idx flattened and stably sorted, order (E) i64 = the flat (m, g, j) position of each; row n sums its contributions in
+ *   that order: the same bits on every run.
+ * crb_vector_pool_voxel_forward: voxel_random_choice. The range test above with R; cell = floorf((local_a + R) / grid_size_a) per
+ *   axis, combined x ny nz + y nz + z and THEN clamped to [0, G - 1]; the first point to reach an empty cell fills it; the scan stops
+ *   after min(nsample, G) filled cells (G when nsample <= 0). new_features (M, G C) the picked rows' features (zeros for empty cells),
+ *   new_local_xyz (M, 3 G), point_cnt (M, G) i32 0 / 1, pick (M, G) i32 the picked global row or -1.
+ * crb_vector_pool_voxel_backward: grad_new_features (M, G C) -> grad_features (N, C); sorted_rows / order (E = M G) from `pick` as
+ *   above. */
+int crb_vector_pool_three_nn(const float* support_xyz, int64_t N, const int32_t* xyz_batch_cnt, const float* new_xyz, int64_t M,
+                             const int32_t* new_xyz_batch_cnt, int B, const float* grid_centers, int G, float query_dist, int nsample,
+                             int neighbor_type, int32_t* idx, float* dist, void* stream);
+int crb_vector_pool_interp_forward(const int32_t* idx, const float* dist, const float* grid_centers, const float* support_xyz,
+                                   const float* features, int64_t N, int64_t M, int G, int C, float* out, void* stream);
+int crb_vector_pool_interp_backward(const float* grad_out, const float* dist, const int32_t* sorted_rows, const int64_t* order,
+                                    int64_t N, int64_t M, int G, int C, float* grad_features, void* stream);
+int crb_vector_pool_voxel_forward(const float* support_xyz, const float* features, int64_t N, const int32_t* xyz_batch_cnt,
+                                  const float* new_xyz, int64_t M, const int32_t* new_xyz_batch_cnt, int B, int num_grid_x,
+                                  int num_grid_y, int num_grid_z, float max_distance, float grid_size_x, float grid_size_y,
+                                  float grid_size_z, int C, int nsample, int neighbor_type, float* new_features, float* new_local_xyz,
+                                  int32_t* point_cnt, int32_t* pick, void* stream);
+int crb_vector_pool_voxel_backward(const float* grad_new_features, const int32_t* sorted_rows, const int64_t* order, int64_t N,
+                                   int64_t M, int G, int C, float* grad_features, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
